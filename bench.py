@@ -18,7 +18,13 @@ launch sequence one at a time (`one_launch_in_flight`: the sequence the roofline
 `python bench.py --gpus N` without a torchrun environment starts the N rank processes itself (before anything touches the
 GPU) and exits non-zero if any of them dies.
 
-Extra objects on the line:
+A plain run sets up, warms up, times exactly K steps in one fenced region and prints the line; `--dump-outputs DIR` then also
+writes what the last timed step computed (rot, trans, size, mask, nocs_coor, ivfc_coor of that launch, float32 .npy; inputs
+and weights are seeded, so two builds can be compared output for output).  Everything else -- the self-checks, the serial,
+roofline, parity, H->D, latency and frames legs, the CPU baseline and the oracle comparisons, and for K < 100 five timed
+regions behind an untimed settle phase -- runs only with `--full` (the `--no-*` switches then leave legs out of it).
+
+Extra objects on the line (`--full`):
   vs_reference -- MEASURED in this run: the oracle's outputs on the batch slot 0 holds against the timed mode's poses of that
                   batch (max / median / p90 / p99 over the crops); likewise inside parity_mode.  null with --no-cpu-baseline.
   roofline     -- dominant kernel class (MFMA GEMM / implicit-GEMM conv / fused MLP): algorithmic FLOP (as the C ABI
@@ -147,6 +153,25 @@ def err_stats(got, ref):
     return {k: (float(f"{v:.3g}") if isinstance(v, float) else v) for k, v in out.items()}
 
 
+DUMP_KEYS = ("rot", "trans", "size", "mask", "nocs_coor", "ivfc_coor")     # what PoseNet.forward hands its caller
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(out, d):
+    """`out` (a forward_device dict, read after a device synchronise) -> d/<key>.npy in float32.  Above DUMP_LIMIT bytes in all, the
+    same crops of every array are kept: a seeded sample, identical in every run with the same arguments."""
+    import numpy as np
+    arrs = {k: out[k].float().cpu().numpy() for k in DUMP_KEYS}
+    n = arrs["rot"].shape[0]
+    keep = min(n, DUMP_LIMIT // (sum(a.nbytes for a in arrs.values()) // n))
+    if keep < n:
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrs = {k: a[idx] for k, a in arrs.items()}
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -169,7 +194,7 @@ def main():
     ap.add_argument("--h2d", default=None, choices=["crops", "frames"],
                     help="put the host -> HBM transfer of every step's inputs INSIDE the timed step (pipelined on a copy stream); "
                          "the line then says so in config.inputs and is not the metric's `value` (inputs resident)")
-    ap.add_argument("--repeat", type=int, default=0, help="timed regions of K steps each (value = their median); 0 = 5 when K < 100, else 1")
+    ap.add_argument("--repeat", type=int, default=0, help="timed regions of K steps each (value = their median); 0 = 5 when K < 100 with --full, else 1")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-check", action="store_true", help="profiling runs only: skip the overlap / grouping self-check (its extra forwards would be counted)")
     ap.add_argument("--no-serial", action="store_true", help="profiling runs only: skip the serial legs")
@@ -179,7 +204,18 @@ def main():
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--no-h2d", action="store_true")
     ap.add_argument("--kernels-out", default=None, help="write the per-label launch table of the roofline pass (all labels) to this JSON file")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the self-checks, every other leg, the CPU baseline and the oracle comparisons "
+                         "(a plain run times the headline alone)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        if args.kernels_out:
+            ap.error("--kernels-out needs --full (it is written by the roofline leg)")
+        args.no_check = args.no_serial = args.no_roofline = args.no_parity = args.no_h2d = args.no_cpu_baseline = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:       # plain `python bench.py --gpus N`: be our own launcher
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -253,10 +289,10 @@ def main():
         for _ in range(3):
             run_single.step()
     calls = [run.step] * n_launch + ([run_single.step] * n_single if run_single is not None else [])
-    # The timed region is EXACTLY K steps, fenced on both sides.  With K < 100 it lasts ~0.1 s: it is then repeated (5 regions, each K
-    # steps, each fenced) and `value` is the MEDIAN region, `value_min` / `value_max` the spread -- one region of 10 launches has no
+    # The timed region is EXACTLY K steps, fenced on both sides.  With --full and K < 100 it lasts ~0.1 s: it is then repeated (5 regions,
+    # each K steps, each fenced) and `value` is the MEDIAN region, `value_min` / `value_max` the spread -- one region of 10 launches has no
     # noise estimate (round-4 review).  `steps` stays K.
-    n_regions = max(1, args.repeat if args.repeat > 0 else (5 if args.steps < 100 else 1))
+    n_regions = max(1, args.repeat if args.repeat > 0 else (5 if args.full and args.steps < 100 else 1))
     # Untimed settle phase (beyond the W warm-up steps): short regions come out up to 20 % slow right after start-up (clocks, caches, the
     # allocator: the round-5 driver line had one of five regions at 0.77 of the median).  Repeat the region untimed-for-the-record until two
     # consecutive ones agree within 1 %, for at most 2 s; every rank runs the same number (the verdict is the max over ranks, all-reduced by timed()).
@@ -271,6 +307,9 @@ def main():
         it = iter(calls)
         dts.append(timed(lambda: next(it)(), len(calls), fence, world, dev))
     dt = statistics.median(dts)
+    if args.dump_outputs and rank == 0:
+        # the last timed call's runner: the single-batch one when an odd K ends with a single-batch launch
+        dump_outputs((run_single if run_single is not None else run).last[1], args.dump_outputs)
     ms_per_step = dt / args.steps * 1e3
     value = world * B * args.steps / dt
     # RCCL really saw `world` ranks: the all-reduced sum of ones (1 without a communicator)
@@ -452,7 +491,7 @@ def main():
                                         "ms_per_step": round(dtg / max(1, n_launch) / G * 1e3, 4)}
         serial = netg
 
-    if rank == 0:
+    if rank == 0 and args.full:
         note("serial leg done")
     # ---------------- roofline leg: per-launch hipEvents on the launch stream, eager pass of the serial net
     # (N > 1: EVERY rank runs the leg -- a handful of eager passes -- so that no rank sits in the final RCCL barrier while rank 0 measures;
@@ -543,7 +582,7 @@ def main():
         line["eager_ms_per_step_sum_of_kernels"] = round(sum(c["ms_per_launch_sequence"] for c in classes.values()) / G, 3)
         line["eager_ms_per_launch_sequence_sum_of_kernels"] = round(sum(c["ms_per_launch_sequence"] for c in classes.values()), 3)
 
-    if rank == 0:
+    if rank == 0 and args.full:
         note("roofline leg done")
     # ---------------- parity modes (rank 0, N = 1; serial; a few steps): the split-operand mode and the fp32 MFMA mode on slot 0's batch
     parity_out = {}
@@ -587,7 +626,7 @@ def main():
             del netp
             torch.cuda.empty_cache()
 
-    if rank == 0:
+    if rank == 0 and args.full:
         note("parity legs done")
     # ---------------- H->D inclusive rates (never `value`): the boundary hands over host tensors.  Same slots, same
     # hipGraphs; every step's inputs come from pinned host memory on a copy stream (givepose_amd.runner.ShardRunner h2d).
@@ -604,7 +643,7 @@ def main():
                          "note": what + "; copy stream -> per-slot staging, overlapped with the other slots' kernels"}
             del rh
 
-    if rank == 0:
+    if rank == 0 and args.full:
         note("h2d legs done")
     # ---------------- latency at the batches evaluate.py feeds (the detections of ONE frame: evaluation/evaluate.py:89-117), hipGraph replay
     if rank == 0 and world == 1 and not args.no_roofline and args.dtype == "f16":

@@ -35,7 +35,7 @@ def test_bench_ranks_without_torchrun(ranks, extra):
     ctx = mp.get_context("forkserver")        # started in conftest.pytest_configure before any GPU call: bench.py is exec'ed from a clean process
     q = ctx.Queue()
     argv = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "6", "--warmup", "2", "--batch", "8", "--inflight", "2",
-            "--no-cpu-baseline", "--no-parity"] + extra
+            "--full", "--no-cpu-baseline", "--no-parity"] + extra
     p = ctx.Process(target=run_cli, args=(argv, {"GP_BENCH_REHEARSE": "1", "WORLD_SIZE": None, "RANK": None, "LOCAL_RANK": None}, q, 700))
     p.start()
     rc, out, err = q.get(timeout=800)
@@ -52,6 +52,61 @@ def test_bench_ranks_without_torchrun(ranks, extra):
         assert line["summary"]["one_batch_in_flight_bs64_serial"] > 0 and line["summary"]["one_launch_in_flight"] > 0
     if "--no-roofline" not in extra:
         assert line["roofline"]["frac"] > 0 and "not the N-rank step" in line["roofline"]["measured_on"]
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_bench_plain_run_times_k_steps_and_dumps_outputs(tmp_path):
+    """A plain run (no --full): exactly K steps in one timed region, none of the --full legs on the line, and --dump-outputs writes the
+    last step's outputs -- with K = 3 and two batches per launch, the single-batch launch of slot 0's first batch (seed 1000) --
+    which a separate forward of that batch reproduces up to the summation order."""
+    import multiprocessing as mp
+    import numpy as np
+    import torch
+    from givepose_amd import PoseNet, PoseNetConfig, synth
+    from givepose_amd.runner import run_cli
+    ctx = mp.get_context("forkserver")
+    q = ctx.Queue()
+    d = tmp_path / "out"
+    argv = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8", "--dump-outputs", str(d)]
+    p = ctx.Process(target=run_cli, args=(argv, {"WORLD_SIZE": None, "RANK": None, "LOCAL_RANK": None}, q, 500))
+    p.start()
+    rc, out, err = q.get(timeout=550)
+    p.join(30)
+    assert rc == 0, err
+    line = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and line["timed_regions"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["unit"] == "images/s" and line["higher_is_better"] is True and line["dtype"] == "f16"
+    assert not {"overlap_check", "one_batch_in_flight", "roofline", "parity_mode", "cpu_baseline", "vs_float64"} & set(line)
+    got = {k: np.load(d / f"{k}.npy") for k in ("rot", "trans", "size", "mask", "nocs_coor", "ivfc_coor")}
+    assert all(a.dtype == np.float32 and a.shape[0] == 8 and np.isfinite(a).all() for a in got.values())
+    net = PoseNet(PoseNetConfig(), dtype=torch.float16, seed=0, use_graph=False).cuda()
+    o = net.forward_device({k: torch.from_numpy(v).cuda() for k, v in synth.synth_batch(8, seed=1000).items()}, "cuda")
+    torch.cuda.synchronize()
+    for k in ("trans", "size"):
+        assert np.abs(o[k].float().cpu().numpy() - got[k]).max() < 3e-2, k
+    assert np.median(np.abs(o["rot"].float().cpu().numpy() - got["rot"]).reshape(8, 9).max(1)) < 8e-3
+
+
+def test_dump_outputs_sample_is_seeded_and_shared(tmp_path, monkeypatch):
+    """Over the size limit, dump_outputs keeps the same crops of every array, and the same ones in every run."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    out = {k: torch.rand((40, 4), generator=g) for k in bench.DUMP_KEYS}
+    out["rot"][:, 0] = torch.arange(40.0)
+    out["mask"] = out["mask"] > 0.5
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 10 * 6 * 16)        # room for 10 of the 40 crops
+    bench.dump_outputs(out, str(tmp_path / "a"))
+    bench.dump_outputs(out, str(tmp_path / "b"))
+    idx = np.load(tmp_path / "a" / "rot.npy")[:, 0].astype(int)
+    assert len(idx) == 10 and len(set(idx)) == 10
+    for k in bench.DUMP_KEYS:
+        a = np.load(tmp_path / "a" / f"{k}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, np.load(tmp_path / "b" / f"{k}.npy"))
+        assert np.array_equal(a, out[k].float().numpy()[idx])
 
 
 def test_bench_helpers_on_cpu():

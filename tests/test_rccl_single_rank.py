@@ -55,7 +55,7 @@ def test_bench_single_rank_on_rccl():
     ctx = mp.get_context("forkserver")
     q = ctx.Queue()
     argv = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "4", "--batch", "8",
-            "--no-cpu-baseline", "--no-parity", "--no-roofline", "--no-h2d"]
+            "--full", "--no-cpu-baseline", "--no-parity", "--no-roofline", "--no-h2d"]
     p = ctx.Process(target=run_cli, args=(argv, {"GP_BENCH_FORCE_COLLECTIVE": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(_free_port()),
                                                  "RANK": "0", "LOCAL_RANK": "0", "WORLD_SIZE": "1"}, q, 800))
     p.start()
