@@ -11,10 +11,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # GP_LIB_PATH: A/B runs of two builds on one box (scripts/race_probe.py); the default is the in-tree library
 LIB_PATH = os.environ.get("GP_LIB_PATH") or os.path.join(_HERE, "libgivepose_hip.so")
 
-ABI_VERSION = 323        # include/givepose_hip.h GP_ABI_VERSION: gp_gemm_desc layout (checked against gp_version() at load)
+ABI_VERSION = 324        # include/givepose_hip.h GP_ABI_VERSION: gp_gemm_desc layout (checked against gp_version() at load)
 GP_F32, GP_F16, GP_F64 = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_LRELU = 0, 1, 2, 3
 EPI_NONE, EPI_GELU, EPI_RELU, EPI_LRELU, EPI_SCALE_RES, EPI_RES_RELU, EPI_LNFOLD_GELU = 0, 1, 2, 3, 4, 5, 6
+ROT_6D, ROT_6D_Y, ROT_6D_Z, ROT_QUAT, ROT_EULER = 0, 1, 2, 3, 4   # enum gp_rot_kind
 KC_GEMM, KC_DCNV3, KC_DWCONV_LN, KC_NORM, KC_ELEMENTWISE, KC_SMALL, KC_COUNT = 0, 1, 2, 3, 4, 5, 6
 KC_NAMES = ["gemm", "dcnv3", "dwconv_ln", "norm", "elementwise", "small"]
 
@@ -67,6 +68,9 @@ PROTOTYPES = {
     "gp_xyz_conv3x3_s2": ([_P] * 3 + [c_int] * 4 + [_P], c_int),
     "gp_size_head": ([_P] * 8 + [c_int] * 5 + [_P], c_int),
     "gp_pose_tail": ([_P, _P, c_int] + [_P] * 10 + [c_int, c_int] + [_P] * 5 + [c_int, _P], c_int),
+    "gp_pose_tail_rt": ([_P, _P, c_int] + [_P] * 10 + [c_int] * 5 + [_P] * 5 + [c_int, _P], c_int),
+    "gp_pnp_conv1_masked": ([_P] * 5 + [c_int] * 4 + [_P], c_int),
+    "gp_pool_mmm": ([_P, _P] + [c_int] * 5 + [_P], c_int),
     "gp_patchify_xyz": ([_P, _P, c_int, c_int, c_int, c_int, _P], c_int),
     "gp_attention64": ([_P, _P, c_int, c_int, c_int, _P], c_int),
     "gp_resnet_stem": ([_P] * 4 + [c_int] * 4 + [_P], c_int),

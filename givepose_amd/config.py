@@ -9,18 +9,53 @@ from dataclasses import dataclass, field
 from typing import Tuple
 
 
+# r_type -> (fc_r width, gp_rot_kind, is_allo): every name get_rot_mat accepts (network/PoseNet.py:36-51); is_allo = "allo" in
+# r_type (PoseNet.py:224).  Kinds: 0 rot6d (rot6d_fixed_x is the same map), 1 fixed-y, 2 fixed-z, 3 quaternion, 4 euler.
+ROT_TYPES = {
+    "allo_rot6d": (6, 0, True), "ego_rot6d": (6, 0, False), "allo_rot6d_sym": (6, 0, True), "allo_rot6d_x": (6, 0, True),
+    "allo_rot6d_sym_y": (6, 1, True), "allo_rot6d_y": (6, 1, True), "allo_rot6d_z": (6, 2, True),
+    "allo_quat": (4, 3, True), "ego_quat": (4, 3, False), "euler": (6, 4, False),
+}
+# flat_op -> pooled statistics per channel of the last ConvPnPNet map (0: the NCHW flatten of all 64 pixels)
+FLAT_OPS = {"flatten": 0, "avg": 1, "avg-max": 2, "avg-max-min": 3}
+
+
+def validate(cfg):
+    """Every reference flag of the config either works or refuses: ValueError for a value the reference does not know,
+    NotImplementedError for one it knows that this build does not run."""
+    def one_of(name, allowed):
+        v = getattr(cfg, name)
+        if v not in allowed:
+            raise ValueError(f"{name}={v!r}: expected one of {sorted(allowed)}")
+    if cfg.mask_attention_type == "concat":
+        raise NotImplementedError("mask_attention_type='concat': the reference builds ConvPnPNet(5, ...) and then feeds it 6 channels "
+                                  "(PoseNet.py:140,162; conv_pnp_net.py:73,152), so it cannot run this mode either")
+    one_of("mask_attention_type", ("none", "mul"))
+    one_of("flat_op", FLAT_OPS)
+    one_of("r_type", ROT_TYPES)
+    one_of("nocsmap_encoder", ("conv", "att"))
+    one_of("use_dcn", ("dcnv3", ""))
+    one_of("t_type", ("site", "center"))
+    if cfg.size_head_out_dim != 3:
+        raise NotImplementedError(f"size_head_out_dim={cfg.size_head_out_dim}: only the 3-D size head is built")
+    if cfg.out_res != 64:
+        raise NotImplementedError(f"out_res={cfg.out_res}: the kernels assume 64 x 64 coordinate maps")
+    if cfg.img_size != 256:
+        raise NotImplementedError(f"img_size={cfg.img_size}: the kernels assume 256 x 256 crops")
+
+
 @dataclass(frozen=True)
 class PoseNetConfig:
     main_backbone: str = "convnext"      # config.py:113 ('convnext' | 'resnet34' throughput variant)
-    img_size: int = 256                  # config.py:20
-    out_res: int = 64                    # config.py:21
-    mask_attention_type: str = "none"    # config.py:22
+    img_size: int = 256                  # config.py:20 (256 only: the kernels assume it)
+    out_res: int = 64                    # config.py:21 (64 only)
+    mask_attention_type: str = "none"    # config.py:22 ('none' | 'mul'; 'concat' refused: the reference cannot run it)
     feat_ts: int = 128                   # config.py:39
-    flat_op: str = "flatten"             # config.py:105
-    t_type: str = "site"                 # config.py:108
-    size_head_out_dim: int = 3           # config.py:109
+    flat_op: str = "flatten"             # config.py:105 ('flatten' | 'avg' | 'avg-max' | 'avg-max-min')
+    t_type: str = "site"                 # config.py:108 ('site' | 'center')
+    size_head_out_dim: int = 3           # config.py:109 (3 only)
     nocsmap_encoder: str = "conv"        # config.py:111 ('conv' | 'att')
-    r_type: str = "allo_rot6d"           # config.py:116
+    r_type: str = "allo_rot6d"           # config.py:116 (any name of ROT_TYPES)
     use_dcn: str = "dcnv3"               # config.py:120 ('dcnv3' | '')
     dataset: str = "CAMERA+Real"         # config.py:9 ('wild6d' rescales z, pose_from_pred_centroid_z.py:110)
     # ConvNeXt-Base (timm convnext_base, network/backbone.py:36-46)
@@ -53,6 +88,16 @@ class PoseNetConfig:
     # the 134 MB hidden tensor never exists (7.2 GB of HBM traffic per 128 crops), but the kernel alone is 8 % slower than the two launches (one wave per SIMD);
     # end to end +0.7 % in flight, -0.8 % serial (docs/history/round5.md 8.5).  Off by default.
     fuse_mlp512: bool = False
+
+    @property
+    def rot_dim(self) -> int:
+        return ROT_TYPES[self.r_type][0] if self.r_type in ROT_TYPES else (4 if "quat" in self.r_type else 6)
+
+    @property
+    def fc_in_dim(self) -> int:
+        """Input width of ConvPnPNet's fc1 / fc1_z (conv_pnp_net.py:100-106)."""
+        k = FLAT_OPS[self.flat_op]
+        return 128 * (k or 64)
 
     @property
     def feature_channel(self) -> int:

@@ -463,7 +463,7 @@ template <typename T, int CIN>
 __global__ __launch_bounds__(256) void smallcin_conv3x3s2_kernel(const float* __restrict__ xyz4,
                                                                 const float* __restrict__ coord2d,
                                                                 const float* __restrict__ wt, T* __restrict__ y,
-                                                                int B, int R, int Cout) {
+                                                                int B, int R, int Cout, const float* __restrict__ mask) {
     constexpr int KK = CIN * 9, PPT = 4;
     extern __shared__ __attribute__((aligned(16))) float w_s[];  // [KK][Cout]
     for (int i = threadIdx.x; i < KK * Cout; i += 256) w_s[i] = wt[i];
@@ -497,6 +497,11 @@ __global__ __launch_bounds__(256) void smallcin_conv3x3s2_kernel(const float* __
                 in[c][3] = ok ? coord2d[((b * 2 + 0) * R + hi) * R + wi] : 0.f;
                 in[c][4] = ok ? coord2d[((b * 2 + 1) * R + hi) * R + wi] : 0.f;
             }
+            if (mask) {                                            // mask_attention_type 'mul': coor_feat * mask, fp32, before the conv
+                const float m = ok ? mask[(b * R + hi) * R + wi] : 0.f;
+#pragma unroll
+                for (int ci = 0; ci < CIN; ++ci) in[c][ci] *= m;
+            }
         }
 #pragma unroll
         for (int kw = 0; kw < 3; ++kw)
@@ -526,7 +531,7 @@ template <int CIN, int NTW>   // NTW: 16-channel tiles per wave (Cout = 64 NTW)
 __global__ __launch_bounds__(256) void smallcin_conv3x3s2_mfma_kernel(const float* __restrict__ xyz4,
                                                                      const float* __restrict__ coord2d,
                                                                      const float* __restrict__ wt, half_t* __restrict__ y,
-                                                                     int B, int R) {
+                                                                     int B, int R, const float* __restrict__ mask) {
     constexpr int RMAX = 64;
     __shared__ __attribute__((aligned(16))) float in_s[5][RMAX + 2][8];
     const int Ro = R / 2, Cout = 64 * NTW;
@@ -545,6 +550,11 @@ __global__ __launch_bounds__(256) void smallcin_conv3x3s2_mfma_kernel(const floa
             if constexpr (CIN == 5) {
                 a[3] = coord2d[(((long)b * 2 + 0) * R + hi) * R + wi];
                 c4[0] = coord2d[(((long)b * 2 + 1) * R + hi) * R + wi];
+            }
+            if (mask) {                                            // mask_attention_type 'mul': all channels times the mask, fp32, before the split
+                const float m = mask[((long)b * R + hi) * R + wi];
+                a *= m;
+                c4 *= m;
             }
         }
         *reinterpret_cast<f32x4*>(&in_s[sr][sc][0]) = a;
@@ -811,6 +821,62 @@ __global__ __launch_bounds__(64) void size_out_kernel(const float* __restrict__ 
 }
 
 // ------------------------------------------------------------------------------------- pose tail
+// network output -> rotation matrix R (row-major), get_rot_mat (network/PoseNet.py:36-51).  kind: enum gp_rot_kind.
+template <int RD>
+__device__ __forceinline__ void decode_rot(const float* o, int kind, float* Ra) {
+    if constexpr (RD == 4) {
+        // quat2mat_torch, eps 0 (pose_utils/pose_utils.py:348-396): q / ||q||, (w, x, y, z)
+        const float n = sqrtf(o[0] * o[0] + o[1] * o[1] + o[2] * o[2] + o[3] * o[3]);
+        const float qw = o[0] / n, qx = o[1] / n, qy = o[2] / n, qz = o[3] / n;
+        const float X = qx * 2.f, Y = qy * 2.f, Z = qz * 2.f;
+        const float wX = qw * X, wY = qw * Y, wZ = qw * Z, xX = qx * X, xY = qx * Y, xZ = qx * Z, yY = qy * Y, yZ = qy * Z, zZ = qz * Z;
+        Ra[0] = 1.f - (yY + zZ); Ra[1] = xY - wZ; Ra[2] = xZ + wY;
+        Ra[3] = xY + wZ; Ra[4] = 1.f - (xX + zZ); Ra[5] = yZ - wX;
+        Ra[6] = xZ - wY; Ra[7] = yZ + wX; Ra[8] = 1.f - (xX + yY);
+    } else if (kind == GP_ROT_EULER) {
+        // euler2mat_batch (pose_utils/rot_reps.py:365-383): angles 0, 2, 1 -> (c1, s1), (c2, s2), (c3, s3); precise sinf / cosf
+        const float c1 = cosf(o[0]), s1 = sinf(o[0]), c2 = cosf(o[2]), s2 = sinf(o[2]), c3 = cosf(o[1]), s3 = sinf(o[1]);
+        Ra[0] = c2 * c3; Ra[1] = -s2; Ra[2] = c2 * s3;
+        Ra[3] = c1 * s2 * c3 + s1 * s3; Ra[4] = c1 * c2; Ra[5] = c1 * s2 * s3 - s1 * c3;
+        Ra[6] = s1 * s2 * c3 - c1 * s3; Ra[7] = s1 * c2; Ra[8] = s1 * s2 * s3 + c1 * c3;
+    } else if (kind == GP_ROT_6D_Y) {
+        // rot6d_fixed_y_to_mat_batch (rot_reps.py:57-67): y = n(y_raw), z = n(y x x_raw), x = z x y
+        const float xr[3] = {o[0], o[1], o[2]};
+        float y[3] = {o[3], o[4], o[5]}, z[3], x[3];
+        float n = fmaxf(sqrtf(y[0] * y[0] + y[1] * y[1] + y[2] * y[2]), 1e-12f);
+        for (int i = 0; i < 3; ++i) y[i] /= n;
+        z[0] = y[1] * xr[2] - y[2] * xr[1]; z[1] = y[2] * xr[0] - y[0] * xr[2]; z[2] = y[0] * xr[1] - y[1] * xr[0];
+        n = fmaxf(sqrtf(z[0] * z[0] + z[1] * z[1] + z[2] * z[2]), 1e-12f);
+        for (int i = 0; i < 3; ++i) z[i] /= n;
+        x[0] = z[1] * y[2] - z[2] * y[1]; x[1] = z[2] * y[0] - z[0] * y[2]; x[2] = z[0] * y[1] - z[1] * y[0];
+        for (int i = 0; i < 3; ++i) { Ra[i * 3] = x[i]; Ra[i * 3 + 1] = y[i]; Ra[i * 3 + 2] = z[i]; }
+    } else if (kind == GP_ROT_6D_Z) {
+        // rot6d_fixed_z_to_mat_batch (rot_reps.py:81-91): y_raw = d6[0:3], z = n(d6[3:6]), x = n(z x y_raw), y = x x z
+        const float yr[3] = {o[0], o[1], o[2]};
+        float z[3] = {o[3], o[4], o[5]}, x[3], y[3];
+        float n = fmaxf(sqrtf(z[0] * z[0] + z[1] * z[1] + z[2] * z[2]), 1e-12f);
+        for (int i = 0; i < 3; ++i) z[i] /= n;
+        x[0] = z[1] * yr[2] - z[2] * yr[1]; x[1] = z[2] * yr[0] - z[0] * yr[2]; x[2] = z[0] * yr[1] - z[1] * yr[0];
+        n = fmaxf(sqrtf(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]), 1e-12f);
+        for (int i = 0; i < 3; ++i) x[i] /= n;
+        y[0] = x[1] * z[2] - x[2] * z[1]; y[1] = x[2] * z[0] - x[0] * z[2]; y[2] = x[0] * z[1] - x[1] * z[0];
+        for (int i = 0; i < 3; ++i) { Ra[i * 3] = x[i]; Ra[i * 3 + 1] = y[i]; Ra[i * 3 + 2] = z[i]; }
+    } else {
+        // rot6d -> R (pose_utils/rot_reps.py:34-55; rot6d_fixed_x_to_mat_batch :69-79 is the same map), F.normalize eps 1e-12
+        float x[3] = {o[0], o[1], o[2]}, yr[3] = {o[3], o[4], o[5]}, z[3], y[3];
+        float n = fmaxf(sqrtf(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]), 1e-12f);
+        for (int i = 0; i < 3; ++i) x[i] /= n;
+        z[0] = x[1] * yr[2] - x[2] * yr[1]; z[1] = x[2] * yr[0] - x[0] * yr[2]; z[2] = x[0] * yr[1] - x[1] * yr[0];
+        n = fmaxf(sqrtf(z[0] * z[0] + z[1] * z[1] + z[2] * z[2]), 1e-12f);
+        for (int i = 0; i < 3; ++i) z[i] /= n;
+        y[0] = z[1] * x[2] - z[2] * x[1]; y[1] = z[2] * x[0] - z[0] * x[2]; y[2] = z[0] * x[1] - z[1] * x[0];
+        for (int i = 0; i < 3; ++i) { Ra[i * 3] = x[i]; Ra[i * 3 + 1] = y[i]; Ra[i * 3 + 2] = z[i]; }
+    }
+}
+
+// RD: width of fc_r (6, or 4 for quaternions).  pred_rot (B,RD) raw fc_r output; rot_allo = the decoded matrix; rot_ego = rot_allo
+// turned to egocentric when is_allo, else rot_allo itself.
+template <int RD>
 __global__ __launch_bounds__(64) void pose_tail_kernel(const float* __restrict__ h, const float* __restrict__ hz,
                                                        int ldh, const float* __restrict__ w_r,
                                                        const float* __restrict__ b_r, const float* __restrict__ w_t,
@@ -818,45 +884,41 @@ __global__ __launch_bounds__(64) void pose_tail_kernel(const float* __restrict__
                                                        const float* __restrict__ b_z, const float* __restrict__ cam_K,
                                                        const float* __restrict__ bbox_center,
                                                        const float* __restrict__ resize_ratio,
-                                                       const float* __restrict__ roi_wh, int wild6d, int site,
-                                                       float* __restrict__ rot6d, float* __restrict__ pred_t,
+                                                       const float* __restrict__ roi_wh, int wild6d, int site, int kind, int is_allo,
+                                                       float* __restrict__ pred_rot, float* __restrict__ pred_t,
                                                        float* __restrict__ rot_allo, float* __restrict__ rot_ego,
                                                        float* __restrict__ trans) {
     const int b = blockIdx.x, lane = threadIdx.x;
     const f32x4 hv = *reinterpret_cast<const f32x4*>(h + (long)b * ldh + lane * 4);
     const f32x4 zv = *reinterpret_cast<const f32x4*>(hz + (long)b * ldh + lane * 4);
-    float o[9];
+    float o[RD + 3];
 #pragma unroll
-    for (int i = 0; i < 9; ++i) {
-        const float* wrow = i < 6 ? w_r + i * 256 : (i < 8 ? w_t + (i - 6) * 256 : w_z);
+    for (int i = 0; i < RD + 3; ++i) {
+        const float* wrow = i < RD ? w_r + i * 256 : (i < RD + 2 ? w_t + (i - RD) * 256 : w_z);
         const f32x4 wv = *reinterpret_cast<const f32x4*>(wrow + lane * 4);
-        const f32x4 xv = i < 8 ? hv : zv;
+        const f32x4 xv = i < RD + 2 ? hv : zv;
         float a = wv[0] * xv[0] + wv[1] * xv[1] + wv[2] * xv[2] + wv[3] * xv[3];
         a = group_sum(a, 64);
-        o[i] = a + (i < 6 ? b_r[i] : (i < 8 ? b_t[i - 6] : b_z[0]));
+        o[i] = a + (i < RD ? b_r[i] : (i < RD + 2 ? b_t[i - RD] : b_z[0]));
     }
     if (lane != 0) return;
-    for (int i = 0; i < 6; ++i) rot6d[b * 6 + i] = o[i];
-    for (int i = 0; i < 3; ++i) pred_t[b * 3 + i] = o[6 + i];
-    // rot6d -> R (pose_utils/rot_reps.py:34-55), F.normalize eps 1e-12
-    float x[3] = {o[0], o[1], o[2]}, yr[3] = {o[3], o[4], o[5]}, z[3], y[3];
-    float n = fmaxf(sqrtf(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]), 1e-12f);
-    for (int i = 0; i < 3; ++i) x[i] /= n;
-    z[0] = x[1] * yr[2] - x[2] * yr[1]; z[1] = x[2] * yr[0] - x[0] * yr[2]; z[2] = x[0] * yr[1] - x[1] * yr[0];
-    n = fmaxf(sqrtf(z[0] * z[0] + z[1] * z[1] + z[2] * z[2]), 1e-12f);
-    for (int i = 0; i < 3; ++i) z[i] /= n;
-    y[0] = z[1] * x[2] - z[2] * x[1]; y[1] = z[2] * x[0] - z[0] * x[2]; y[2] = z[0] * x[1] - z[1] * x[0];
+    for (int i = 0; i < RD; ++i) pred_rot[b * RD + i] = o[i];
+    for (int i = 0; i < 3; ++i) pred_t[b * 3 + i] = o[RD + i];
     float Ra[9];
-    for (int i = 0; i < 3; ++i) { Ra[i * 3] = x[i]; Ra[i * 3 + 1] = y[i]; Ra[i * 3 + 2] = z[i]; }
+    decode_rot<RD>(o, kind, Ra);
     for (int i = 0; i < 9; ++i) rot_allo[b * 9 + i] = Ra[i];
     // centroid / z back-projection (pose_from_pred_centroid_z.py:75-121)
     const float* K = cam_K + b * 9;
-    const float c0 = site ? o[6] : o[6] * 0.f, c1 = site ? o[7] : o[7] * 0.f;
+    const float c0 = site ? o[RD] : o[RD] * 0.f, c1 = site ? o[RD + 1] : o[RD + 1] * 0.f;
     const float cx = c0 * roi_wh[b * 2] + bbox_center[b * 2], cy = c1 * roi_wh[b * 2 + 1] + bbox_center[b * 2 + 1];
-    float zz = o[8] * resize_ratio[b];
+    float zz = o[RD + 2] * resize_ratio[b];
     if (wild6d) zz = zz * cam_K[0] / 590.f;
     const float tr[3] = {zz * (cx - K[2]) / K[0], zz * (cy - K[5]) / K[4], zz};
     for (int i = 0; i < 3; ++i) trans[b * 3 + i] = tr[i];
+    if (!is_allo) {      // ego_* / euler: the network's matrix is the egocentric rotation (PoseNet.py:224)
+        for (int i = 0; i < 9; ++i) rot_ego[b * 9 + i] = Ra[i];
+        return;
+    }
     // allocentric -> egocentric (pose_utils/utils.py:29-84): float32 ray, float64 rotation
     const float tn = sqrtf(tr[0] * tr[0] + tr[1] * tr[1] + tr[2] * tr[2]);
     const float ray[3] = {tr[0] / tn, tr[1] / tn, tr[2] / tn};
@@ -878,6 +940,70 @@ __global__ __launch_bounds__(64) void pose_tail_kernel(const float* __restrict__
             }
     } else {
         for (int i = 0; i < 9; ++i) rot_ego[b * 9 + i] = Ra[i];
+    }
+}
+
+// ------------------------------------------------------------------------------------- ConvPnPNet flat_op pooling
+// (B, HW, C) channels-last -> (B, k*C) rows [mean | max | min] over the HW pixels (conv_pnp_net.py:175-187), fp32 accumulation.
+// One workgroup per crop: LPR = C / VEC lanes cover one pixel's channels with 16-byte loads, 256 / LPR pixel groups (16 at fp16
+// C = 128: four loads per lane, all in flight at once) walk the pixels; a butterfly over the groups of a wave (lane xor LPR, ...),
+// then the four waves' partials meet in LDS and wave 0 writes.  No atomics.
+template <typename T>
+__global__ __launch_bounds__(256) void pool_mmm_kernel(const T* __restrict__ x, T* __restrict__ out, int HW, int C, int k) {
+    constexpr int VEC = Vec16<T>::N;
+    __shared__ float red[4][3][64 * VEC];
+    const int LPR = C / VEC, G = 256 / LPR;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
+    const int g = tid / LPR, c0 = (tid - g * LPR) * VEC;
+    float sm[VEC], mx[VEC], mn[VEC];
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) { sm[e] = 0.f; mx[e] = -INFINITY; mn[e] = INFINITY; }
+    const T* xb = x + (long)b * HW * C + c0;
+#pragma unroll 4
+    for (int px = g; px < HW; px += G) {
+        const Vec16<T> v = load16(xb + (long)px * C);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            const float f = v.get(e);
+            sm[e] += f;
+            mx[e] = fmaxf(mx[e], f);
+            mn[e] = fminf(mn[e], f);
+        }
+    }
+    for (int off = LPR; off < 64; off <<= 1)
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            sm[e] += __shfl_xor(sm[e], off, 64);
+            mx[e] = fmaxf(mx[e], __shfl_xor(mx[e], off, 64));
+            mn[e] = fminf(mn[e], __shfl_xor(mn[e], off, 64));
+        }
+    if (lane < LPR) {
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) { red[wave][0][c0 + e] = sm[e]; red[wave][1][c0 + e] = mx[e]; red[wave][2][c0 + e] = mn[e]; }
+    }
+    __syncthreads();
+    if (wave != 0 || lane >= LPR) return;
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+        const int c = c0 + e;
+        sm[e] = (red[0][0][c] + red[1][0][c]) + (red[2][0][c] + red[3][0][c]);
+        mx[e] = fmaxf(fmaxf(red[0][1][c], red[1][1][c]), fmaxf(red[2][1][c], red[3][1][c]));
+        mn[e] = fminf(fminf(red[0][2][c], red[1][2][c]), fminf(red[2][2][c], red[3][2][c]));
+    }
+    T* o = out + (long)b * k * C + c0;
+    Vec16<T> v;
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) v.set(e, sm[e] / (float)HW);
+    store16(o, v);
+    if (k > 1) {
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) v.set(e, mx[e]);
+        store16(o + C, v);
+    }
+    if (k > 2) {
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) v.set(e, mn[e]);
+        store16(o + 2 * C, v);
     }
 }
 
@@ -1017,7 +1143,7 @@ extern "C" int gp_pointwise_k3(const float* xyz4, const float* w, const float* b
 
 template <int CIN>
 static int launch_smallcin(const float* xyz4, const float* coord2d, const float* w, void* y, int B, int R, int Cout,
-                           int dtype, void* stream, const char* name) {
+                           int dtype, void* stream, const char* name, const float* mask = nullptr) {
     GP_REQUIRE(xyz4 && w && y && B > 0 && R % 8 == 0, "%s: bad argument", name);
     GP_DT_OK(dtype);
     GP_REQUIRE(Cout % 4 == 0 && Cout / 4 <= 256 && 256 % (Cout / 4) == 0, "%s: Cout=%d", name, Cout);
@@ -1027,12 +1153,12 @@ static int launch_smallcin(const float* xyz4, const float* coord2d, const float*
     gp_timing_before(s, GP_KC_SMALL, 2.0 * pix * CIN * 9 * Cout, (double)B * R * R * CIN * 4 + (double)pix * Cout * (dtype == GP_F16 ? 2 : 4));
     static const bool mfma = [] { const char* e = getenv("GP_SMALLCIN_MFMA"); return !(e && e[0] == '0'); }();   // A/B switch
     if (dtype == GP_F16 && mfma && R == 64 && (Cout == 128 || Cout == 256)) {   // 64 x 64 maps -> 32 x 32: two output rows per workgroup
-        if (Cout == 128) hipLaunchKernelGGL((smallcin_conv3x3s2_mfma_kernel<CIN, 2>), dim3(B * (R / 4)), dim3(256), 0, s, xyz4, coord2d, w, (half_t*)y, B, R);
-        else hipLaunchKernelGGL((smallcin_conv3x3s2_mfma_kernel<CIN, 4>), dim3(B * (R / 4)), dim3(256), 0, s, xyz4, coord2d, w, (half_t*)y, B, R);
+        if (Cout == 128) hipLaunchKernelGGL((smallcin_conv3x3s2_mfma_kernel<CIN, 2>), dim3(B * (R / 4)), dim3(256), 0, s, xyz4, coord2d, w, (half_t*)y, B, R, mask);
+        else hipLaunchKernelGGL((smallcin_conv3x3s2_mfma_kernel<CIN, 4>), dim3(B * (R / 4)), dim3(256), 0, s, xyz4, coord2d, w, (half_t*)y, B, R, mask);
     } else if (dtype == GP_F16)
-        hipLaunchKernelGGL((smallcin_conv3x3s2_kernel<half_t, CIN>), dim3(cdiv(pix / 4, 256 / (Cout / 4))), dim3(256), lds, s, xyz4, coord2d, w, (half_t*)y, B, R, Cout);
+        hipLaunchKernelGGL((smallcin_conv3x3s2_kernel<half_t, CIN>), dim3(cdiv(pix / 4, 256 / (Cout / 4))), dim3(256), lds, s, xyz4, coord2d, w, (half_t*)y, B, R, Cout, mask);
     else
-        hipLaunchKernelGGL((smallcin_conv3x3s2_kernel<float, CIN>), dim3(cdiv(pix / 4, 256 / (Cout / 4))), dim3(256), lds, s, xyz4, coord2d, w, (float*)y, B, R, Cout);
+        hipLaunchKernelGGL((smallcin_conv3x3s2_kernel<float, CIN>), dim3(cdiv(pix / 4, 256 / (Cout / 4))), dim3(256), lds, s, xyz4, coord2d, w, (float*)y, B, R, Cout, mask);
     GP_LAUNCH_CHECK(name);
 }
 
@@ -1040,6 +1166,26 @@ extern "C" int gp_pnp_conv1(const float* xyz4, const float* coord2d, const float
                             int Cout, int dtype, void* stream) {
     GP_REQUIRE(coord2d != nullptr, "gp_pnp_conv1: null coord2d");
     return launch_smallcin<5>(xyz4, coord2d, w, y, B, R, Cout, dtype, stream, "gp_pnp_conv1");
+}
+
+extern "C" int gp_pnp_conv1_masked(const float* xyz4, const float* coord2d, const float* mask, const float* w, void* y, int B,
+                                   int R, int Cout, int dtype, void* stream) {
+    GP_REQUIRE(coord2d != nullptr && mask != nullptr, "gp_pnp_conv1_masked: null coord2d / mask");
+    return launch_smallcin<5>(xyz4, coord2d, w, y, B, R, Cout, dtype, stream, "gp_pnp_conv1_masked", mask);
+}
+
+extern "C" int gp_pool_mmm(const void* x, void* out, int B, int HW, int C, int k, int dtype, void* stream) {
+    GP_REQUIRE(x && out && B > 0 && HW > 0 && k >= 1 && k <= 3, "gp_pool_mmm: bad argument");
+    GP_DT_OK(dtype);
+    const int vec = dtype == GP_F16 ? 8 : 4, lpr = C / vec;
+    GP_REQUIRE(C > 0 && C % vec == 0 && lpr <= 64 && 64 % lpr == 0, "gp_pool_mmm: C=%d (C / %d must divide 64)", C, vec);
+    GP_REQUIRE(((size_t)x & 15) == 0 && ((size_t)out & 15) == 0, "gp_pool_mmm: 16-byte alignment");
+    hipStream_t s = (hipStream_t)stream;
+    const int esz = dtype == GP_F16 ? 2 : 4;
+    gp_timing_before(s, GP_KC_SMALL, 3.0 * B * HW * C, (double)B * (HW + k) * C * esz);
+    if (dtype == GP_F16) hipLaunchKernelGGL(pool_mmm_kernel<half_t>, dim3(B), dim3(256), 0, s, (const half_t*)x, (half_t*)out, HW, C, k);
+    else hipLaunchKernelGGL(pool_mmm_kernel<float>, dim3(B), dim3(256), 0, s, (const float*)x, (float*)out, HW, C, k);
+    GP_LAUNCH_CHECK("gp_pool_mmm");
 }
 
 extern "C" int gp_xyz_conv3x3_s2(const float* xyz4, const float* w, void* y, int B, int R, int Cout, int dtype,
@@ -1064,19 +1210,35 @@ extern "C" int gp_size_head(const void* feat, const float* w1, const float* b1, 
     GP_LAUNCH_CHECK("gp_size_head");
 }
 
+extern "C" int gp_pose_tail_rt(const float* h, const float* hz, int ldh, const float* w_r, const float* b_r,
+                               const float* w_t, const float* b_t, const float* w_z, const float* b_z,
+                               const float* cam_K, const float* bbox_center, const float* resize_ratio,
+                               const float* roi_wh, int wild6d, int site_centroid, int rot_dim, int rot_kind, int is_allo,
+                               float* pred_rot, float* pred_t, float* rot_allo, float* rot_ego, float* trans, int B, void* stream) {
+    GP_REQUIRE(h && hz && w_r && b_r && w_t && b_t && w_z && b_z && cam_K && bbox_center && resize_ratio && roi_wh &&
+                   pred_rot && pred_t && rot_allo && rot_ego && trans && B > 0 && ldh >= 256 && ldh % 4 == 0,
+               "gp_pose_tail_rt: bad argument");
+    GP_REQUIRE((rot_dim == 4 && rot_kind == GP_ROT_QUAT) ||
+                   (rot_dim == 6 && (rot_kind == GP_ROT_6D || rot_kind == GP_ROT_6D_Y || rot_kind == GP_ROT_6D_Z || rot_kind == GP_ROT_EULER)),
+               "gp_pose_tail_rt: rot_dim %d does not go with rot_kind %d", rot_dim, rot_kind);
+    hipStream_t s = (hipStream_t)stream;
+    gp_timing_before(s, GP_KC_SMALL, 2.0 * B * (rot_dim + 3) * 256, B * 2048.0);
+    if (rot_dim == 4)
+        hipLaunchKernelGGL(pose_tail_kernel<4>, dim3(B), dim3(64), 0, s, h, hz, ldh, w_r, b_r, w_t, b_t, w_z, b_z, cam_K,
+                           bbox_center, resize_ratio, roi_wh, wild6d, site_centroid, rot_kind, is_allo, pred_rot, pred_t, rot_allo, rot_ego, trans);
+    else
+        hipLaunchKernelGGL(pose_tail_kernel<6>, dim3(B), dim3(64), 0, s, h, hz, ldh, w_r, b_r, w_t, b_t, w_z, b_z, cam_K,
+                           bbox_center, resize_ratio, roi_wh, wild6d, site_centroid, rot_kind, is_allo, pred_rot, pred_t, rot_allo, rot_ego, trans);
+    GP_LAUNCH_CHECK("gp_pose_tail_rt");
+}
+
 extern "C" int gp_pose_tail(const float* h, const float* hz, int ldh, const float* w_r, const float* b_r,
                             const float* w_t, const float* b_t, const float* w_z, const float* b_z,
                             const float* cam_K, const float* bbox_center, const float* resize_ratio,
                             const float* roi_wh, int wild6d, int site_centroid, float* rot6d, float* pred_t,
                             float* rot_allo, float* rot_ego, float* trans, int B, void* stream) {
-    GP_REQUIRE(h && hz && w_r && b_r && w_t && b_t && w_z && b_z && cam_K && bbox_center && resize_ratio && roi_wh &&
-                   rot6d && pred_t && rot_allo && rot_ego && trans && B > 0 && ldh >= 256 && ldh % 4 == 0,
-               "gp_pose_tail: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    gp_timing_before(s, GP_KC_SMALL, 2.0 * B * 9 * 256, B * 2048.0);
-    hipLaunchKernelGGL(pose_tail_kernel, dim3(B), dim3(64), 0, s, h, hz, ldh, w_r, b_r, w_t, b_t, w_z, b_z, cam_K,
-                       bbox_center, resize_ratio, roi_wh, wild6d, site_centroid, rot6d, pred_t, rot_allo, rot_ego, trans);
-    GP_LAUNCH_CHECK("gp_pose_tail");
+    return gp_pose_tail_rt(h, hz, ldh, w_r, b_r, w_t, b_t, w_z, b_z, cam_K, bbox_center, resize_ratio, roi_wh, wild6d,
+                           site_centroid, 6, GP_ROT_6D, 1, rot6d, pred_t, rot_allo, rot_ego, trans, B, stream);
 }
 
 extern "C" int gp_patchify_xyz(const float* xyz4, void* out, int B, int R, int P, int dtype, void* stream) {

@@ -15,7 +15,7 @@ from ._lib import (ACT_GELU, ACT_LRELU, ACT_NONE, ACT_RELU, EPI_GELU, EPI_LNFOLD
 
 __all__ = ["dtype_code", "gemm", "conv2d_nhwc", "dcnv3_forward", "dcnv3_backward", "dcnv3_forward_into", "convnext_stem", "dwconv_ln",
            "layernorm", "groupnorm", "upsample_bilinear2x", "deconv_col2im", "xyz_out_layer", "pointwise_k3",
-           "pnp_conv1", "xyz_conv3x3_s2", "size_head", "pose_tail", "mask_resize_nearest"]
+           "pnp_conv1", "pnp_conv1_masked", "pool_mmm", "xyz_conv3x3_s2", "size_head", "pose_tail", "pose_tail_rt", "mask_resize_nearest"]
 
 
 def _L():
@@ -530,6 +530,21 @@ def pnp_conv1(xyz4, coord2d, w, out, B, R):
     return out
 
 
+def pnp_conv1_masked(xyz4, coord2d, mask, w, out, B, R):
+    check(_L().gp_pnp_conv1_masked(_ptr(xyz4), _ptr(_contig(coord2d, "coord2d")), _ptr(_contig(_chk(mask, "mask", torch.float32), "mask")),
+                                   _ptr(w), _ptr(out), B, R, w.shape[1], dtype_code(out.dtype), _stream()), "gp_pnp_conv1_masked")
+    return out
+
+
+def pool_mmm(x, out, k):
+    """x (B, HW, C) channels-last -> out (B, k*C): [mean | max | min][:k] over the HW pixels (ConvPnPNet flat_op)."""
+    B, HW, C = x.shape
+    if x.dtype != out.dtype or tuple(out.shape) != (B, k * C):
+        raise ValueError(f"pool_mmm: out {tuple(out.shape)} {out.dtype} for x {tuple(x.shape)} {x.dtype}, k={k}")
+    check(_L().gp_pool_mmm(_ptr(_contig(x, "x")), _ptr(_contig(out, "out")), B, HW, C, k, dtype_code(x.dtype), _stream()), "gp_pool_mmm")
+    return out
+
+
 def xyz_conv3x3_s2(xyz4, w, out, B, R):
     check(_L().gp_xyz_conv3x3_s2(_ptr(xyz4), _ptr(w), _ptr(out), B, R, w.shape[1], dtype_code(out.dtype), _stream()),
           "gp_xyz_conv3x3_s2")
@@ -550,6 +565,15 @@ def pose_tail(h, hz, ldh, W, cam_K, bbox_center, resize_ratio, roi_wh, wild6d, s
                             _ptr(W["fc_z.w"]), _ptr(W["fc_z.b"]), _ptr(cam_K), _ptr(bbox_center), _ptr(resize_ratio),
                             _ptr(roi_wh), int(wild6d), int(site), _ptr(outs["rot6d"]), _ptr(outs["pred_t"]),
                             _ptr(outs["rot_allo"]), _ptr(outs["rot_ego"]), _ptr(outs["trans"]), B, _stream()), "gp_pose_tail")
+
+
+def pose_tail_rt(h, hz, ldh, W, cam_K, bbox_center, resize_ratio, roi_wh, wild6d, site, rot_dim, kind, is_allo, outs, B):
+    """pose_tail for any rotation type: outs["pred_rot"] (B, rot_dim) instead of outs["rot6d"] (gp_pose_tail_rt)."""
+    check(_L().gp_pose_tail_rt(_ptr(h), _ptr(hz), ldh, _ptr(W["fc_r.w"]), _ptr(W["fc_r.b"]), _ptr(W["fc_t.w"]), _ptr(W["fc_t.b"]),
+                               _ptr(W["fc_z.w"]), _ptr(W["fc_z.b"]), _ptr(cam_K), _ptr(bbox_center), _ptr(resize_ratio),
+                               _ptr(roi_wh), int(wild6d), int(site), int(rot_dim), int(kind), int(is_allo), _ptr(outs["pred_rot"]),
+                               _ptr(outs["pred_t"]), _ptr(outs["rot_allo"]), _ptr(outs["rot_ego"]), _ptr(outs["trans"]), B, _stream()),
+          "gp_pose_tail_rt")
 
 
 def resnet_stem(img, w, b, out):

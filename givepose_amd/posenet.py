@@ -21,7 +21,7 @@ import torch.nn as nn
 
 from . import _lib, ops, synth
 from ._lib import (ACT_GELU, ACT_RELU, EPI_GELU, EPI_LNFOLD_GELU, EPI_LRELU, EPI_NONE, EPI_SCALE_RES)
-from .config import PoseNetConfig
+from .config import FLAT_OPS, ROT_TYPES, PoseNetConfig, validate
 
 OM_LD = 128     # row length of the DCNv3 offset | mask projection output (108 used columns)
 
@@ -73,6 +73,7 @@ class PoseNet(nn.Module):
         # defined but never wired there) is this build's throughput variant with feature_channel 512
         if cfg.main_backbone not in ("convnext", "resnet34"):
             raise NotImplementedError(f"unknown backbone {cfg.main_backbone}")
+        validate(cfg)        # the pose-head flags (flat_op, mask_attention_type, r_type, ...): each works or refuses
         if cfg.res_fp32 and (dtype != torch.float16 or cfg.defer_ln or cfg.main_backbone != "convnext"):
             raise ValueError("res_fp32 is an option of the float16 ConvNeXt path (without defer_ln)")
         self.cfg = cfg
@@ -254,9 +255,13 @@ class PoseNet(nn.Module):
             if li > 0:
                 W[f"pnp.c{li}_w"] = gw(sd[f"pnp_net.features.{i}.weight"].permute(0, 2, 3, 1).reshape(128, -1))
             W[f"pnp.g{li}_w"], W[f"pnp.g{li}_b"] = f32(sd[f"pnp_net.features.{i + 1}.weight"]), f32(sd[f"pnp_net.features.{i + 1}.bias"])
-        # fc1 || fc1_z as one GEMM; columns permuted from the reference's NCHW flatten (c*64+hw,
-        # conv_pnp_net.py:170-172) to the channels-last flatten (hw*128+c) used on the device
-        perm = lambda w: w.reshape(-1, 128, 64).permute(0, 2, 1).reshape(-1, 8192)
+        # fc1 || fc1_z as one GEMM; flat_op 'flatten': columns permuted from the reference's NCHW flatten (c*64+hw,
+        # conv_pnp_net.py:170-172) to the channels-last flatten (hw*128+c) used on the device.  The pooled modes' columns
+        # [mean c0..127 | max | min] are already in the order gp_pool_mmm writes
+        if cfg.flat_op == "flatten":
+            perm = lambda w: w.reshape(-1, 128, 64).permute(0, 2, 1).reshape(-1, 8192)
+        else:
+            perm = lambda w: w
         W["pnp.fc1_w"] = gw(torch.cat([perm(sd["pnp_net.fc1.weight"]), perm(sd["pnp_net.fc1_z.weight"])], 0))
         W["pnp.fc1_b"] = f32(torch.cat([sd["pnp_net.fc1.bias"], sd["pnp_net.fc1_z.bias"]], 0))
         W["pnp.fc2_w"], W["pnp.fc2_b"] = gw(sd["pnp_net.fc2.weight"]), f32(sd["pnp_net.fc2.bias"])
@@ -349,7 +354,10 @@ class PoseNet(nn.Module):
         buf["p0"], buf["p1"], buf["p2"] = e(B, 32, 32, 128), e(B, 16, 16, 128), e(B, 8, 8, 128)
         buf["fc1"] = e(B, 2048)
         buf["hh"], buf["hz"] = f(B, 256), f(B, 256)
-        buf["rot6d"], buf["pred_t"], buf["rot_allo"], buf["rot_ego"], buf["trans"] = f(B, 6), f(B, 3), f(B, 9), f(B, 9), f(B, 3)
+        if FLAT_OPS[cfg.flat_op]:     # flat_op avg / avg-max / avg-max-min: the pooled fc1 input (storage type; fp32 in split mode: gp_gemm splits X)
+            buf["pooled"] = e(B, 128 * FLAT_OPS[cfg.flat_op])
+        buf["pred_rot"], buf["pred_t"], buf["rot_allo"], buf["rot_ego"], buf["trans"] = f(B, cfg.rot_dim), f(B, 3), f(B, 9), f(B, 9), f(B, 3)
+        buf["rot6d"] = buf["pred_rot"] if cfg.rot_dim == 6 else None
         plan = {"buf": buf, "graph": None, "warm": False, "ragged": bool(ragged)}
         if ragged:
             # crop -> first crop of its batch (gp_dwconv_ln_groups); rewritten before every launch, the pointer is what the graph holds.
@@ -606,23 +614,33 @@ class PoseNet(nn.Module):
                 self._gn(y, W[q + "gn_w"], W[q + "gn_b"], ACT_RELU, buf, out=cat2d[:, 256:], ldy=512, fused=fused)
 
     def _seq_pnp(self, B, plan):
-        """ivfc_nhwc4 + roi_coord_2d -> rot6d / pred_t / rot / trans: ConvPnPNet (network/conv_pnp_net.py:137-201) + pose decode."""
+        """ivfc_nhwc4 + roi_coord_2d (+ mask_out) -> pred_rot / pred_t / rot / trans: ConvPnPNet (network/conv_pnp_net.py:137-201)
+        + pose decode."""
         W, buf, cfg = self._packed, plan["buf"], self.cfg
         R = cfg.out_res
-        p = ops.pnp_conv1(buf["ivfc_nhwc4"], buf["roi_coord_2d"], W["pnp.c0_w"], buf["p0"], B, R)
+        k = FLAT_OPS[cfg.flat_op]
+        if cfg.mask_attention_type == "mul":     # coor_feat * mask_attention (conv_pnp_net.py:146-154), applied while the conv stages its input
+            p = ops.pnp_conv1_masked(buf["ivfc_nhwc4"], buf["roi_coord_2d"], buf["mask_out"], W["pnp.c0_w"], buf["p0"], B, R)
+        else:
+            p = ops.pnp_conv1(buf["ivfc_nhwc4"], buf["roi_coord_2d"], W["pnp.c0_w"], buf["p0"], B, R)
         self._gn(p, W["pnp.g0_w"], W["pnp.g0_b"], ACT_RELU, buf)
         for li in (1, 2):
             hw = nxt_hw = (32 >> li) ** 2
             rows = self._gnrows(B * hw, 128, 9 * 128, hw)
             nxt = ops.conv2d_nhwc(p, W[f"pnp.c{li}_w"], 3, 3, 2, 1, out=buf[f"p{li}"], gn=self._gnarg(buf, hw, rows),
-                                  prefetch=W["pnp.c2_w"] if li == 1 else W["pnp.fc1_w"])     # (fc1: the first 4 of its 33 MB)
+                                  prefetch=W["pnp.c2_w"] if li == 1 else W["pnp.fc1_w"])     # (fc1: the first 4 of its 33 MB; all of it pooled)
             self._gn(nxt, W[f"pnp.g{li}_w"], W[f"pnp.g{li}_b"], ACT_RELU, buf, fused=True, rows=rows)
             p = nxt
-        ops.gemm(p.view(B, 8192), W["pnp.fc1_w"], buf["fc1"], bias=W["pnp.fc1_b"], epilogue=EPI_LRELU, prefetch=W["pnp.fc2_w"])
+        if k:    # flat_op avg / avg-max / avg-max-min: [mean | max | min] over the 64 pixels, fc1 at K = 128 k
+            x = ops.pool_mmm(p.view(B, 64, 128), buf["pooled"], k)
+        else:
+            x = p.view(B, 8192)
+        ops.gemm(x, W["pnp.fc1_w"], buf["fc1"], bias=W["pnp.fc1_b"], epilogue=EPI_LRELU, prefetch=W["pnp.fc2_w"])
         ops.gemm(buf["fc1"], W["pnp.fc2_w"], buf["hh"], bias=W["pnp.fc2_b"], epilogue=EPI_LRELU, M=B, K=1024, ldx=2048, prefetch=W["pnp.fc2z_w"])
         ops.gemm(buf["fc1"][:, 1024:], W["pnp.fc2z_w"], buf["hz"], bias=W["pnp.fc2z_b"], epilogue=EPI_LRELU, M=B, K=1024, ldx=2048)
-        ops.pose_tail(buf["hh"], buf["hz"], 256, W, buf["cam_K"], buf["bbox_center"], buf["resize_ratio"], buf["roi_wh"],
-                      cfg.dataset == "wild6d", cfg.t_type == "site", buf, B)
+        rot_dim, kind, is_allo = ROT_TYPES[cfg.r_type]
+        ops.pose_tail_rt(buf["hh"], buf["hz"], 256, W, buf["cam_K"], buf["bbox_center"], buf["resize_ratio"], buf["roi_wh"],
+                         cfg.dataset == "wild6d", cfg.t_type == "site", rot_dim, kind, is_allo, buf, B)
 
     # ------------------------------------------------------------------ public API
     _INPUT_KEYS = ("roi_img", "roi_mask", "roi_coord_2d", "cam_K", "roi_wh", "bbox_center", "resize_ratio", "mean_size")
@@ -722,7 +740,8 @@ class PoseNet(nn.Module):
         n = n_real
         feat = buf.get(f"x{len(self.cfg.convnext_dims) - 1}")
         return {"rot": buf["rot_ego"].view(B, 3, 3)[:n], "trans": buf["trans"][:n], "size": buf["size"][:n], "mask": buf["mask_out"][:n],
-                "nocs_coor": buf["nocs_nchw"][:n], "ivfc_coor": buf["ivfc_nchw"][:n], "rot6d": buf["rot6d"][:n], "pred_t": buf["pred_t"][:n],
+                "nocs_coor": buf["nocs_nchw"][:n], "ivfc_coor": buf["ivfc_nchw"][:n], "rot6d": None if buf["rot6d"] is None else buf["rot6d"][:n],
+                "pred_rot": buf["pred_rot"][:n], "pred_t": buf["pred_t"][:n],
                 "rot_allo": buf["rot_allo"].view(B, 3, 3)[:n], "feat": None if feat is None else feat[:n],
                 "feat_cat": buf["feat_cat"][:n]}
 
@@ -772,19 +791,24 @@ class PoseNet(nn.Module):
         return buf[f"e_o{layer}"].permute(0, 3, 1, 2).float().contiguous()
 
     @torch.no_grad()
-    def run_pnp(self, x_nchw, data, device="cuda"):
+    def run_pnp(self, x_nchw, data, device="cuda", mask=None):
         """ConvPnPNet.forward (network/conv_pnp_net.py:137-201) on x = cat(coor, roi_coord_2d) (B,5,64,64): returns
-        (rot6d (B,6), t (B,3)); `data` supplies the camera scalars the fused pose tail also reads."""
+        (pred_rot (B,rot_dim), t (B,3)); `data` supplies the camera scalars the fused pose tail also reads.  mask (B,1,64,64):
+        the mask_attention input, required when mask_attention_type='mul'."""
         B = x_nchw.shape[0]
+        if self.cfg.mask_attention_type == "mul" and mask is None:
+            raise ValueError("run_pnp: mask_attention_type='mul' needs the (B,1,64,64) mask")
         plan = self._module_plan(B, device)
         buf = plan["buf"]
+        if mask is not None:
+            buf["mask_out"].copy_(mask.reshape(buf["mask_out"].shape))
         for k in ("cam_K", "roi_wh", "bbox_center", "resize_ratio"):
             buf[k].copy_(data[k].reshape(buf[k].shape))
         buf["ivfc_nhwc4"].zero_()
         buf["ivfc_nhwc4"][:, :3] = x_nchw[:, :3].to(device).float().permute(0, 2, 3, 1).reshape(-1, 3)
         buf["roi_coord_2d"].copy_(x_nchw[:, 3:5])
         self._seq_pnp(B, plan)
-        return buf["rot6d"].clone(), buf["pred_t"].clone()
+        return buf["pred_rot"].clone(), buf["pred_t"].clone()
 
     def static_inputs(self, B, device="cuda", slot=0, ragged=False):
         """The plan's device-resident input buffers (fill these to skip the per-call H->D copies).  ragged: the buffers of the

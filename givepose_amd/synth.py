@@ -168,8 +168,9 @@ def param_manifest(cfg: PoseNetConfig = PoseNetConfig()):
         m[f"pnp_net.features.{i}.weight"] = (128, 5 if li == 0 else 128, 3, 3)
         m[f"pnp_net.features.{i + 1}.weight"] = (128,)
         m[f"pnp_net.features.{i + 1}.bias"] = (128,)
-    for n, shp in (("fc1", (1024, 8192)), ("fc2", (256, 1024)), ("fc1_z", (1024, 8192)),
-                   ("fc2_z", (256, 1024)), ("fc_z", (1, 256)), ("fc_r", (6, 256)), ("fc_t", (2, 256))):
+    fin = cfg.fc_in_dim          # flat_op: 8192 | 128 | 256 | 384 (conv_pnp_net.py:100-106)
+    for n, shp in (("fc1", (1024, fin)), ("fc2", (256, 1024)), ("fc1_z", (1024, fin)),
+                   ("fc2_z", (256, 1024)), ("fc_z", (1, 256)), ("fc_r", (cfg.rot_dim, 256)), ("fc_t", (2, 256))):
         m[f"pnp_net.{n}.weight"] = shp
         m[f"pnp_net.{n}.bias"] = (shp[0],)
     return m

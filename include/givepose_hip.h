@@ -50,7 +50,7 @@ enum gp_epilogue {
 };
 
 const char* gp_last_error(void);
-#define GP_ABI_VERSION 323 /* round 6: + gp_dwconv_ln_groups (322), gp_convnext_mlp_pack_w2_s32 / GP_MLP_S32 (323); 321 = round 5: gp_gemm_desc.gn_rows + gp_gemm_gn_rows (321); gp_gemm variants 19-22, gp_convnext_mlp C = 512 (no layout change); 311 = round 4 (+ gp_groupnorm_upsample2x); 310 = round 3 (gp_gemm_desc: split-operand / fp32 residual stream fields); 200 = round 2 */
+#define GP_ABI_VERSION 324 /* 324: + gp_pnp_conv1_masked, gp_pool_mmm, gp_pose_tail_rt; round 6: + gp_dwconv_ln_groups (322), gp_convnext_mlp_pack_w2_s32 / GP_MLP_S32 (323); 321 = round 5: gp_gemm_desc.gn_rows + gp_gemm_gn_rows (321); gp_gemm variants 19-22, gp_convnext_mlp C = 512 (no layout change); 311 = round 4 (+ gp_groupnorm_upsample2x); 310 = round 3 (gp_gemm_desc: split-operand / fp32 residual stream fields); 200 = round 2 */
 int gp_version(void);   /* == GP_ABI_VERSION of the header the library was built from */
 /* device properties the host needs: CU count and arch string ("gfx950...") */
 int gp_device_info(int* cu_count, char* arch, int arch_len);
@@ -301,6 +301,15 @@ int gp_pointwise_k3(const float* xyz4, const float* w, const float* b, void* y, 
 int gp_pnp_conv1(const float* xyz4, const float* coord2d, const float* w, void* y, int B, int R, int Cout,
                  int dtype, void* stream);
 
+/* gp_pnp_conv1 with ConvPnPNet's mask_attention_type 'mul' (conv_pnp_net.py:146-154): every one of the 5 input channels is
+ * multiplied by mask (B,1,R,R) fp32 at its pixel, in fp32, before the convolution.  With an all-ones mask: gp_pnp_conv1's bits. */
+int gp_pnp_conv1_masked(const float* xyz4, const float* coord2d, const float* mask, const float* w, void* y, int B, int R,
+                        int Cout, int dtype, void* stream);
+
+/* ConvPnPNet flat_op pooling (conv_pnp_net.py:175-187): x (B,HW,C) channels-last of `dtype` -> out (B,k*C) of `dtype`, the rows
+ * [mean c0..C-1 | max | min] for k = 1 ('avg'), 2 ('avg-max'), 3 ('avg-max-min'); fp32 accumulation.  C / (16 / esz) divides 64. */
+int gp_pool_mmm(const void* x, void* out, int B, int HW, int C, int k, int dtype, void* stream);
+
 /* Plain Conv2d(3,Cout,3,s2,p1,bias=False) on the (B*HW,4) fp32 coordinate map: first MAPEncoder layer
  * when use_dcn='' (conv_pnp_net.py:258-272). w (27, Cout) fp32 tap-major. */
 int gp_xyz_conv3x3_s2(const float* xyz4, const float* w, void* y, int B, int R, int Cout, int dtype,
@@ -322,6 +331,20 @@ int gp_pose_tail(const float* h, const float* hz, int ldh, const float* w_r, con
                  const float* bbox_center, const float* resize_ratio, const float* roi_wh, int wild6d,
                  int site_centroid, float* rot6d, float* pred_t, float* rot_allo, float* rot_ego,
                  float* trans, int B, void* stream);
+
+/* Rotation decodes of get_rot_mat (network/PoseNet.py:36-51).  GP_ROT_6D: rot6d_to_mat_batch, also the r_types
+ * allo_rot6d_x / ego_rot6d / allo_rot6d_sym (rot6d_fixed_x_to_mat_batch is the same map); GP_ROT_6D_Y: rot6d_fixed_y_to_mat_batch;
+ * GP_ROT_6D_Z: rot6d_fixed_z_to_mat_batch; GP_ROT_QUAT: quat2mat_torch (eps 0, rot_dim 4); GP_ROT_EULER: euler2mat_batch. */
+enum gp_rot_kind { GP_ROT_6D = 0, GP_ROT_6D_Y = 1, GP_ROT_6D_Z = 2, GP_ROT_QUAT = 3, GP_ROT_EULER = 4 };
+
+/* gp_pose_tail for every rotation type: fc_r is (rot_dim, 256) (rot_dim 4 with GP_ROT_QUAT, else 6); pred_rot (B,rot_dim) the raw
+ * fc_r output; rot_allo (B,9) the decoded matrix before any conversion; rot_ego (B,9) that matrix turned egocentric when is_allo
+ * ("allo" in r_type, PoseNet.py:224), else rot_allo itself.  gp_pose_tail is the (6, GP_ROT_6D, is_allo 1) call. */
+int gp_pose_tail_rt(const float* h, const float* hz, int ldh, const float* w_r, const float* b_r,
+                    const float* w_t, const float* b_t, const float* w_z, const float* b_z, const float* cam_K,
+                    const float* bbox_center, const float* resize_ratio, const float* roi_wh, int wild6d,
+                    int site_centroid, int rot_dim, int rot_kind, int is_allo, float* pred_rot, float* pred_t,
+                    float* rot_allo, float* rot_ego, float* trans, int B, void* stream);
 
 /* MAPTransformerEncoer front end (network/attention_pnp_net.py:126-157, PatchEmbed :264-302): gather the PxP patches
  * of the (B*R*R,4) fp32 coordinate map into GEMM rows (B*(R/P)^2, P*P*3) of `dtype`, k = (ky*P+kx)*3 + c. */
