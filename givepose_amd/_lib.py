@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # GP_LIB_PATH: A/B runs of two builds on one box (scripts/race_probe.py); the default is the in-tree library
 LIB_PATH = os.environ.get("GP_LIB_PATH") or os.path.join(_HERE, "libgivepose_hip.so")
 
-ABI_VERSION = 324        # include/givepose_hip.h GP_ABI_VERSION: gp_gemm_desc layout (checked against gp_version() at load)
+ABI_VERSION = 325        # include/givepose_hip.h GP_ABI_VERSION: gp_gemm_desc layout (checked against gp_version() at load)
 GP_F32, GP_F16, GP_F64 = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_LRELU = 0, 1, 2, 3
 EPI_NONE, EPI_GELU, EPI_RELU, EPI_LRELU, EPI_SCALE_RES, EPI_RES_RELU, EPI_LNFOLD_GELU = 0, 1, 2, 3, 4, 5, 6
@@ -73,6 +73,8 @@ PROTOTYPES = {
     "gp_pool_mmm": ([_P, _P] + [c_int] * 5 + [_P], c_int),
     "gp_patchify_xyz": ([_P, _P, c_int, c_int, c_int, c_int, _P], c_int),
     "gp_attention64": ([_P, _P, c_int, c_int, c_int, _P], c_int),
+    "gp_attention64_hd": ([_P, _P] + [c_int] * 4 + [_P], c_int),
+    "gp_patchify_pnp": ([_P, _P, _P] + [c_int] * 4 + [_P], c_int),
     "gp_resnet_stem": ([_P] * 4 + [c_int] * 4 + [_P], c_int),
     "gp_maxpool3x3s2": ([_P, _P] + [c_int] * 5 + [_P], c_int),
     "gp_mask_resize_nearest": ([_P, _P, c_int, c_int, c_int, _P], c_int),

@@ -42,6 +42,18 @@ def validate(cfg):
         raise NotImplementedError(f"out_res={cfg.out_res}: the kernels assume 64 x 64 coordinate maps")
     if cfg.img_size != 256:
         raise NotImplementedError(f"img_size={cfg.img_size}: the kernels assume 256 x 256 crops")
+    one_of("pnp_head", ("conv", "att"))
+    if cfg.pnp_head == "att":       # AttentionPnPNet (network/attention_pnp_net.py:36-124)
+        if cfg.flat_op != "flatten":
+            raise NotImplementedError(f"pnp_head='att' with flat_op={cfg.flat_op!r}: AttentionPnPNet.forward_head reduces over the channel axis of "
+                                      "its (B, 64, 192) tokens (attention_pnp_net.py:90-106), so fc1 gets 64 columns where it expects "
+                                      f"{192 * FLAT_OPS[cfg.flat_op]}; the reference cannot run it either")
+        if cfg.mask_attention_type == "mul":
+            raise NotImplementedError("pnp_head='att' with mask_attention_type='mul': AttentionPnPNet.forward takes no mask "
+                                      "(attention_pnp_net.py:121)")
+        if ROT_TYPES[cfg.r_type][0] != 6:
+            raise NotImplementedError(f"pnp_head='att' with r_type={cfg.r_type!r}: AttentionPnPNet's fc_r is Linear(256, 6) whatever the "
+                                      "rotation type (attention_pnp_net.py:72), and a quaternion needs 4 outputs")
 
 
 @dataclass(frozen=True)
@@ -88,6 +100,10 @@ class PoseNetConfig:
     # the 134 MB hidden tensor never exists (7.2 GB of HBM traffic per 128 crops), but the kernel alone is 8 % slower than the two launches (one wave per SIMD);
     # end to end +0.7 % in flight, -0.8 % serial (docs/history/round5.md 8.5).  Off by default.
     fuse_mlp512: bool = False
+    # build-side switch (not a reference flag: PoseNet.py:162 always builds ConvPnPNet and the reference has no flag for this head):
+    # 'att' runs AttentionPnPNet(img_size=64, patch_size=8, in_chans=5, embed_dim=192, depth=3, num_heads=8, flat_op='flatten')
+    # (network/attention_pnp_net.py:36-124) in ConvPnPNet's place, on the same cat(ivfc, roi_coord_2d) input.  'conv' | 'att'
+    pnp_head: str = "conv"
 
     @property
     def rot_dim(self) -> int:
@@ -95,8 +111,10 @@ class PoseNetConfig:
 
     @property
     def fc_in_dim(self) -> int:
-        """Input width of ConvPnPNet's fc1 / fc1_z (conv_pnp_net.py:100-106)."""
+        """Input width of ConvPnPNet's fc1 / fc1_z (conv_pnp_net.py:100-106); AttentionPnPNet: 64 tokens x 192 (attention_pnp_net.py:54-59)."""
         k = FLAT_OPS[self.flat_op]
+        if self.pnp_head == "att":
+            return 192 * (k or 64)
         return 128 * (k or 64)
 
     @property

@@ -628,17 +628,21 @@ __global__ __launch_bounds__(256) void patchify_kernel(const float* __restrict__
 }
 
 // one wavefront per (batch, head); lane = query token.  K and V of the head are staged in LDS as fp32; each lane
-// keeps its 64 scores in registers (two-pass softmax), so nothing but q/k/v/out touches memory.
-template <typename T>
+// keeps its 64 scores in registers (two-pass softmax), so nothing but q/k/v/out touches memory.  HD: head_dim, 32 for
+// MAPTransformerEncoer (gp_attention64), 24 for AttentionPnPNet (192 channels in 8 heads; gp_attention64_hd).
+template <int HD> struct AttScale;
+template <> struct AttScale<32> { static constexpr float v = 0.17677669529663687f; };   // 32 ** -0.5
+template <> struct AttScale<24> { static constexpr float v = 0.20412414523193151f; };   // 24 ** -0.5
+template <typename T, int HD>
 __global__ __launch_bounds__(64) void attention64_kernel(const T* __restrict__ qkv, T* __restrict__ out, int heads) {
-    __shared__ float ks[64][33], vs[64][33];
+    __shared__ float ks[64][HD + 1], vs[64][HD + 1];
     const int b = blockIdx.x / heads, h = blockIdx.x - b * heads, i = threadIdx.x;
-    const int C3 = 3 * heads * 32, C = heads * 32;
-    const T* row = qkv + ((long)b * 64 + i) * C3 + h * 32;
-    float q[32];
+    const int C3 = 3 * heads * HD, C = heads * HD;
+    const T* row = qkv + ((long)b * 64 + i) * C3 + h * HD;
+    float q[HD];
 #pragma unroll
-    for (int d = 0; d < 32; ++d) {
-        q[d] = (float)row[d] * 0.17677669529663687f;   // head_dim ** -0.5
+    for (int d = 0; d < HD; ++d) {
+        q[d] = (float)row[d] * AttScale<HD>::v;   // head_dim ** -0.5
         ks[i][d] = (float)row[C + d];
         vs[i][d] = (float)row[2 * C + d];
     }
@@ -648,7 +652,7 @@ __global__ __launch_bounds__(64) void attention64_kernel(const T* __restrict__ q
     for (int j = 0; j < 64; ++j) {
         float a = 0.f;
 #pragma unroll
-        for (int d = 0; d < 32; ++d) a = fmaf(q[d], ks[j][d], a);
+        for (int d = 0; d < HD; ++d) a = fmaf(q[d], ks[j][d], a);
         s[j] = a;
         mx = fmaxf(mx, a);
     }
@@ -659,18 +663,39 @@ __global__ __launch_bounds__(64) void attention64_kernel(const T* __restrict__ q
         sum += s[j];
     }
     const float inv = 1.0f / sum;
-    float o[32];
+    float o[HD];
 #pragma unroll
-    for (int d = 0; d < 32; ++d) o[d] = 0.f;
+    for (int d = 0; d < HD; ++d) o[d] = 0.f;
 #pragma unroll
     for (int j = 0; j < 64; ++j) {
         const float pj = s[j] * inv;
 #pragma unroll
-        for (int d = 0; d < 32; ++d) o[d] = fmaf(pj, vs[j][d], o[d]);
+        for (int d = 0; d < HD; ++d) o[d] = fmaf(pj, vs[j][d], o[d]);
     }
-    T* orow = out + ((long)b * 64 + i) * C + h * 32;
+    T* orow = out + ((long)b * 64 + i) * C + h * HD;
 #pragma unroll
-    for (int d = 0; d < 32; ++d) store_T(orow + d, o[d]);
+    for (int d = 0; d < HD; ++d) store_T(orow + d, o[d]);
+}
+
+// AttentionPnPNet front end: the 5-channel PnP input cat(ivfc coordinates, roi_coord_2d) (PoseNet.py:196-197) as PxP patch rows
+// (B*(R/P)^2, P*P*5), k = (ky*P+kx)*5 + c; channels 0-2 from the (B*R*R,4) fp32 map, 3-4 from the NCHW (B,2,R,R) fp32 grid.
+template <typename T>
+__global__ __launch_bounds__(256) void patchify_pnp_kernel(const float* __restrict__ xyz4, const float* __restrict__ coord2d,
+                                                           T* __restrict__ out, int B, int R, int P) {
+    const int K = P * P * 5, np = R / P;
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)B * np * np * P * P) return;
+    const int pp = (int)(idx % (P * P));
+    long t = idx / (P * P);
+    const int px = (int)(t % np); t /= np;
+    const int py = (int)(t % np);
+    const long b = t / np;
+    const int ky = pp / P, kx = pp - ky * P;
+    const long pix = (long)(py * P + ky) * R + px * P + kx;
+    const f32x4 v = *reinterpret_cast<const f32x4*>(xyz4 + (b * R * R + pix) * 4);
+    const float u = coord2d[(b * 2) * R * R + pix], w = coord2d[(b * 2 + 1) * R * R + pix];
+    T* o = out + ((b * np + py) * np + px) * K + pp * 5;
+    store_T(o, v[0]); store_T(o + 1, v[1]); store_T(o + 2, v[2]); store_T(o + 3, u); store_T(o + 4, w);
 }
 
 // ------------------------------------------------------------------------------------- ResNet stem / maxpool
@@ -1257,9 +1282,32 @@ extern "C" int gp_attention64(const void* qkv, void* out, int B, int heads, int 
     GP_DT_OK(dtype);
     hipStream_t s = (hipStream_t)stream;
     gp_timing_before(s, GP_KC_SMALL, 4.0 * B * heads * 64 * 64 * 32, (double)B * 64 * heads * 32 * 4 * (dtype == GP_F16 ? 2 : 4));
-    if (dtype == GP_F16) hipLaunchKernelGGL(attention64_kernel<half_t>, dim3(B * heads), dim3(64), 0, s, (const half_t*)qkv, (half_t*)out, heads);
-    else hipLaunchKernelGGL(attention64_kernel<float>, dim3(B * heads), dim3(64), 0, s, (const float*)qkv, (float*)out, heads);
+    if (dtype == GP_F16) hipLaunchKernelGGL((attention64_kernel<half_t, 32>), dim3(B * heads), dim3(64), 0, s, (const half_t*)qkv, (half_t*)out, heads);
+    else hipLaunchKernelGGL((attention64_kernel<float, 32>), dim3(B * heads), dim3(64), 0, s, (const float*)qkv, (float*)out, heads);
     GP_LAUNCH_CHECK("gp_attention64");
+}
+
+extern "C" int gp_attention64_hd(const void* qkv, void* out, int B, int heads, int head_dim, int dtype, void* stream) {
+    GP_REQUIRE(qkv && out && B > 0 && heads > 0, "gp_attention64_hd: bad argument");
+    GP_REQUIRE(head_dim == 24 || head_dim == 32, "gp_attention64_hd: head_dim=%d (24 or 32)", head_dim);
+    GP_DT_OK(dtype);
+    if (head_dim == 32) return gp_attention64(qkv, out, B, heads, dtype, stream);
+    hipStream_t s = (hipStream_t)stream;
+    gp_timing_before(s, GP_KC_SMALL, 4.0 * B * heads * 64 * 64 * 24, (double)B * 64 * heads * 24 * 4 * (dtype == GP_F16 ? 2 : 4));
+    if (dtype == GP_F16) hipLaunchKernelGGL((attention64_kernel<half_t, 24>), dim3(B * heads), dim3(64), 0, s, (const half_t*)qkv, (half_t*)out, heads);
+    else hipLaunchKernelGGL((attention64_kernel<float, 24>), dim3(B * heads), dim3(64), 0, s, (const float*)qkv, (float*)out, heads);
+    GP_LAUNCH_CHECK("gp_attention64_hd");
+}
+
+extern "C" int gp_patchify_pnp(const float* xyz4, const float* coord2d, void* out, int B, int R, int P, int dtype, void* stream) {
+    GP_REQUIRE(xyz4 && coord2d && out && B > 0 && P > 0 && R % P == 0, "gp_patchify_pnp: bad argument");
+    GP_DT_OK(dtype);
+    hipStream_t s = (hipStream_t)stream;
+    const long total = (long)B * R * R;
+    gp_timing_before(s, GP_KC_ELEMENTWISE, 0.0, total * (24.0 + 5 * (dtype == GP_F16 ? 2 : 4)));
+    if (dtype == GP_F16) hipLaunchKernelGGL(patchify_pnp_kernel<half_t>, dim3(cdiv(total, 256)), dim3(256), 0, s, xyz4, coord2d, (half_t*)out, B, R, P);
+    else hipLaunchKernelGGL(patchify_pnp_kernel<float>, dim3(cdiv(total, 256)), dim3(256), 0, s, xyz4, coord2d, (float*)out, B, R, P);
+    GP_LAUNCH_CHECK("gp_patchify_pnp");
 }
 
 extern "C" int gp_resnet_stem(const float* img, const float* w, const float* b, void* out, int B, int H, int W, int dtype,

@@ -1293,6 +1293,60 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const TI* __restrict__ x
     store16p<T>(y, row * ldy + cs * VEC, o, pl);
 }
 
+// Row LayerNorm at widths whose count of 16-byte vectors CT = C / VEC is not a power of two (C = 192: the AttentionPnPNet tokens,
+// 24 vectors in fp16, 48 in fp32).  A row gets the next power of two CTP > CT of lanes; the CTP - CT extra lanes load nothing, hold
+// zeros and skip the mean subtraction, so they add exactly 0 to both sums.  layernorm_kernel keeps the power-of-two widths.
+template <typename T, typename TI = T>
+__global__ __launch_bounds__(256) void layernorm_padded_kernel(const TI* __restrict__ x, const float* __restrict__ w,
+                                                               const float* __restrict__ b, T* __restrict__ y,
+                                                               long rows, int C, int CTP, float eps, int ldy, long pl) {
+    constexpr int VEC = Vec16<T>::N;
+    __shared__ float red[4];
+    const int CT = C / VEC, PG = 256 / CTP;
+    const int cs = threadIdx.x % CTP;
+    const long row = (long)blockIdx.x * PG + threadIdx.x / CTP;
+    const bool live = row < rows && cs < CT;
+    float a[VEC];
+    if (live) {
+        if constexpr (std::is_same<T, TI>::value) {
+            const Vec16<T> v = load16<T>(x + row * C + cs * VEC);
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) a[e] = v.get(e);
+        } else {
+            static_assert(sizeof(TI) == 4 && VEC == 8, "mixed form: fp32 in, fp16 out");
+            const f32x4 v0 = *reinterpret_cast<const f32x4*>(x + row * C + cs * VEC), v1 = *reinterpret_cast<const f32x4*>(x + row * C + cs * VEC + 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { a[e] = v0[e]; a[e + 4] = v1[e]; }
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) a[e] = 0.f;
+    }
+    float s[1] = {0.f};
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) s[0] += a[e];
+    pixel_group_sum<1>(s, CTP, red);
+    const float mean = s[0] / C;
+    float q[1] = {0.f};
+    if (live) {
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            a[e] -= mean;
+            q[0] += a[e] * a[e];
+        }
+    }
+    pixel_group_sum<1>(q, CTP, red);
+    if (!live) return;
+    const float rstd = rsqrtf(q[0] / C + eps);
+    float gw[VEC], gb[VEC];
+    load_f32<T>(w + cs * VEC, gw);
+    load_f32<T>(b + cs * VEC, gb);
+    Vec16<T> o;
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) o.set(e, a[e] * rstd * gw[e] + gb[e]);
+    store16p<T>(y, row * ldy + cs * VEC, o, pl);
+}
+
 // GroupNorm scale / shift arithmetic.  fp16 storage: every rounding pinned (explicit fma), because gp_groupnorm_upsample2x must agree bit for
 // bit with gp_groupnorm_apply and hipcc contracts `a * b + c` differently from one instantiation to the next.  fp32 storage keeps the
 // plain expressions of rounds 1-3 (nothing has to agree with them, and the parity modes' measured errors stay what they were).
@@ -2022,9 +2076,23 @@ extern "C" int gp_layernorm(const void* x, const float* w, const float* b, void*
     GP_REQUIRE(!(dtype_in & GP_IN_F32) || (dtype == GP_F16 && x != y), "gp_layernorm: GP_IN_F32 (fp32 input rows) goes with GP_F16 output, y != x");
     const long pl = (dtype_in & GP_OUT_PLANES) ? rows * C : 0;
     const int esz = dtype == GP_F16 ? 2 : 4;
-    GP_REQUIRE(ct_ok(C, esz), "gp_layernorm: unsupported C=%d", C);
-    const int CT = C / (16 / esz), PG = 256 / CT;
     hipStream_t s = (hipStream_t)stream;
+    if (!ct_ok(C, esz)) {    // C % (16 / esz) == 0 with a vector count that is no power of two: the zero-padded lane group
+        const int CT = C > 0 && C % (16 / esz) == 0 ? C / (16 / esz) : 0;
+        GP_REQUIRE(CT >= 1 && CT <= 256, "gp_layernorm: unsupported C=%d (needs C %% %d == 0, C <= %d)", C, 16 / esz, 256 * (16 / esz));
+        int CTP = 1;
+        while (CTP < CT) CTP <<= 1;
+        const int PG = 256 / CTP;
+        gp_timing_before(s, GP_KC_NORM, 8.0 * rows * C, (double)rows * C * esz * 2);
+        if (dtype == GP_F16 && (dtype_in & GP_IN_F32))
+            hipLaunchKernelGGL((layernorm_padded_kernel<half_t, float>), dim3(cdiv(rows, PG)), dim3(256), 0, s, (const float*)x, w, b, (half_t*)y, rows, C, CTP, eps, ldy, 0l);
+        else if (dtype == GP_F16)
+            hipLaunchKernelGGL(layernorm_padded_kernel<half_t>, dim3(cdiv(rows, PG)), dim3(256), 0, s, (const half_t*)x, w, b, (half_t*)y, rows, C, CTP, eps, ldy, 0l);
+        else
+            hipLaunchKernelGGL(layernorm_padded_kernel<float>, dim3(cdiv(rows, PG)), dim3(256), 0, s, (const float*)x, w, b, (float*)y, rows, C, CTP, eps, ldy, pl);
+        GP_LAUNCH_CHECK("gp_layernorm");
+    }
+    const int CT = C / (16 / esz), PG = 256 / CT;
     gp_timing_before(s, GP_KC_NORM, 8.0 * rows * C, (double)rows * C * esz * 2);
     if (dtype == GP_F16 && (dtype_in & GP_IN_F32))
         hipLaunchKernelGGL((layernorm_kernel<half_t, float>), dim3(cdiv(rows, PG)), dim3(256), 0, s, (const float*)x, w, b, (half_t*)y, rows, C, eps, ldy, 0l);

@@ -456,6 +456,20 @@ def attention64(qkv, out, B, heads):
     return out
 
 
+def attention64_hd(qkv, out, B, heads, head_dim):
+    """softmax(q k^T * head_dim^-0.5) v per (crop, head) over 64 tokens; head_dim 24 (AttentionPnPNet) or 32 (= attention64)."""
+    check(_L().gp_attention64_hd(_ptr(_contig(qkv, "qkv")), _ptr(out), B, heads, head_dim, dtype_code(qkv.dtype), _stream()),
+          "gp_attention64_hd")
+    return out
+
+
+def patchify_pnp(xyz4, coord2d, out, B, R, P):
+    """(B*R*R,4) fp32 coordinates + (B,2,R,R) fp32 roi_coord_2d -> (B*(R/P)^2, P*P*5) patch rows, k = (ky*P+kx)*5 + c."""
+    check(_L().gp_patchify_pnp(_ptr(_contig(xyz4, "xyz4")), _ptr(_contig(coord2d, "coord2d")), _ptr(out), B, R, P, dtype_code(out.dtype),
+                               _stream()), "gp_patchify_pnp")
+    return out
+
+
 def groupnorm_chunks(B, HW):
     return _L().gp_groupnorm_chunks(B, HW)
 

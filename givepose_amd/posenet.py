@@ -250,15 +250,32 @@ class PoseNet(nn.Module):
                 W[q + "conv_w"] = f32(cw.reshape(256, -1).t()) if li == 0 else gw(cw.permute(0, 2, 3, 1).reshape(256, -1))
             W[q + "gn_w"], W[q + "gn_b"] = f32(sd[f"nocs_encoder.features.{i + 1}.weight"]), f32(sd[f"nocs_encoder.features.{i + 1}.bias"])
         W["red.w"], W["red.b"] = gw(sd["feat_reducer.weight"].reshape(256, -1)), f32(sd["feat_reducer.bias"])
-        W["pnp.c0_w"] = f32(sd["pnp_net.features.0.weight"].reshape(128, -1).t())
-        for li, i in enumerate((0, 3, 6)):
-            if li > 0:
-                W[f"pnp.c{li}_w"] = gw(sd[f"pnp_net.features.{i}.weight"].permute(0, 2, 3, 1).reshape(128, -1))
-            W[f"pnp.g{li}_w"], W[f"pnp.g{li}_b"] = f32(sd[f"pnp_net.features.{i + 1}.weight"]), f32(sd[f"pnp_net.features.{i + 1}.bias"])
+        if cfg.pnp_head == "att":      # AttentionPnPNet (network/attention_pnp_net.py:36-124): the MAPTransformerEncoer layout at 192 channels
+            a = lambda k: sd["pnp_net." + k]
+            W["apn.pe_w"] = gw(a("patch_embed.proj.weight").permute(0, 2, 3, 1).reshape(192, -1))   # K = (ky,kx,c): gp_patchify_pnp's rows
+            W["apn.pe_b"] = f32(a("patch_embed.proj.bias"))
+            W["apn.pos"] = f32(a("pos_embed").reshape(64, 192))                                      # tiled per batch in _plan
+            W["apn.ones"] = torch.ones(192, dtype=torch.float32, device=device)
+            W["apn.norm_w"], W["apn.norm_b"] = f32(a("norm.weight")), f32(a("norm.bias"))
+            for i in range(3):
+                q = f"apn{i}."
+                for n in ("norm1", "norm2"):
+                    W[q + n + "_w"], W[q + n + "_b"] = f32(a(f"block.{i}.{n}.weight")), f32(a(f"block.{i}.{n}.bias"))
+                W[q + "qkv_w"] = gw(a(f"block.{i}.attn.qkv.weight"))
+                W[q + "proj_w"], W[q + "proj_b"] = gw(a(f"block.{i}.attn.proj.weight")), f32(a(f"block.{i}.attn.proj.bias"))
+                W[q + "fc1_w"], W[q + "fc1_b"] = gw(a(f"block.{i}.mlp.fc1.weight")), f32(a(f"block.{i}.mlp.fc1.bias"))
+                W[q + "fc2_w"], W[q + "fc2_b"] = gw(a(f"block.{i}.mlp.fc2.weight")), f32(a(f"block.{i}.mlp.fc2.bias"))
+        else:
+            W["pnp.c0_w"] = f32(sd["pnp_net.features.0.weight"].reshape(128, -1).t())
+            for li, i in enumerate((0, 3, 6)):
+                if li > 0:
+                    W[f"pnp.c{li}_w"] = gw(sd[f"pnp_net.features.{i}.weight"].permute(0, 2, 3, 1).reshape(128, -1))
+                W[f"pnp.g{li}_w"], W[f"pnp.g{li}_b"] = f32(sd[f"pnp_net.features.{i + 1}.weight"]), f32(sd[f"pnp_net.features.{i + 1}.bias"])
         # fc1 || fc1_z as one GEMM; flat_op 'flatten': columns permuted from the reference's NCHW flatten (c*64+hw,
         # conv_pnp_net.py:170-172) to the channels-last flatten (hw*128+c) used on the device.  The pooled modes' columns
-        # [mean c0..127 | max | min] are already in the order gp_pool_mmm writes
-        if cfg.flat_op == "flatten":
+        # [mean c0..127 | max | min] are already in the order gp_pool_mmm writes.  The attention head's flatten(1) of its
+        # (B, 64, 192) tokens (token*192+c) IS the device's row order: no permutation
+        if cfg.flat_op == "flatten" and cfg.pnp_head == "conv":
             perm = lambda w: w.reshape(-1, 128, 64).permute(0, 2, 1).reshape(-1, 8192)
         else:
             perm = lambda w: w
@@ -351,7 +368,12 @@ class PoseNet(nn.Module):
             buf["a_qkv"], buf["a_att"], buf["a_mlp"] = e(B * 64, 768), e(B * 64, 256), e(B * 64, 1024)
             buf["a_pos"] = self._packed["att.pos"].to(T).repeat(B, 1).contiguous()      # pos_embed per token row
         buf["feat_cat"] = e(B, 8, 8, 512)
-        buf["p0"], buf["p1"], buf["p2"] = e(B, 32, 32, 128), e(B, 16, 16, 128), e(B, 8, 8, 128)
+        if cfg.pnp_head == "att":     # AttentionPnPNet: 64 tokens x 192 per crop; p_flat (B*64, 192) viewed as (B, 12288) is fc1's input
+            buf["p_patch"], buf["p_x"], buf["p_h"] = e(B * 64, 320), e(B * 64, 192), e(B * 64, 192)
+            buf["p_qkv"], buf["p_att"], buf["p_mlp"], buf["p_flat"] = e(B * 64, 576), e(B * 64, 192), e(B * 64, 768), e(B * 64, 192)
+            buf["p_pos"] = self._packed["apn.pos"].to(T).repeat(B, 1).contiguous()      # pos_embed per token row
+        else:
+            buf["p0"], buf["p1"], buf["p2"] = e(B, 32, 32, 128), e(B, 16, 16, 128), e(B, 8, 8, 128)
         buf["fc1"] = e(B, 2048)
         buf["hh"], buf["hz"] = f(B, 256), f(B, 256)
         if FLAT_OPS[cfg.flat_op]:     # flat_op avg / avg-max / avg-max-min: the pooled fc1 input (storage type; fp32 in split mode: gp_gemm splits X)
@@ -619,6 +641,9 @@ class PoseNet(nn.Module):
         W, buf, cfg = self._packed, plan["buf"], self.cfg
         R = cfg.out_res
         k = FLAT_OPS[cfg.flat_op]
+        if cfg.pnp_head == "att":
+            self._seq_att_pnp(B, plan)
+            return
         if cfg.mask_attention_type == "mul":     # coor_feat * mask_attention (conv_pnp_net.py:146-154), applied while the conv stages its input
             p = ops.pnp_conv1_masked(buf["ivfc_nhwc4"], buf["roi_coord_2d"], buf["mask_out"], W["pnp.c0_w"], buf["p0"], B, R)
         else:
@@ -638,6 +663,32 @@ class PoseNet(nn.Module):
         ops.gemm(x, W["pnp.fc1_w"], buf["fc1"], bias=W["pnp.fc1_b"], epilogue=EPI_LRELU, prefetch=W["pnp.fc2_w"])
         ops.gemm(buf["fc1"], W["pnp.fc2_w"], buf["hh"], bias=W["pnp.fc2_b"], epilogue=EPI_LRELU, M=B, K=1024, ldx=2048, prefetch=W["pnp.fc2z_w"])
         ops.gemm(buf["fc1"][:, 1024:], W["pnp.fc2z_w"], buf["hz"], bias=W["pnp.fc2z_b"], epilogue=EPI_LRELU, M=B, K=1024, ldx=2048)
+        rot_dim, kind, is_allo = ROT_TYPES[cfg.r_type]
+        ops.pose_tail_rt(buf["hh"], buf["hz"], 256, W, buf["cam_K"], buf["bbox_center"], buf["resize_ratio"], buf["roi_wh"],
+                         cfg.dataset == "wild6d", cfg.t_type == "site", rot_dim, kind, is_allo, buf, B)
+
+    def _seq_att_pnp(self, B, plan):
+        """AttentionPnPNet.forward (network/attention_pnp_net.py:79-124) on cat(ivfc, roi_coord_2d) (PoseNet.py:196-197): patch embed +
+        pos_embed, 3 pre-norm ViT blocks (192 = 8 heads x 24), LayerNorm, flatten(1), the exact-GELU fc tail, then the pose decode."""
+        W, buf, cfg = self._packed, plan["buf"], self.cfg
+        x = buf["p_x"]
+        ops.patchify_pnp(buf["ivfc_nhwc4"], buf["roi_coord_2d"], buf["p_patch"], B, cfg.out_res, 8)
+        ops.gemm(buf["p_patch"], W["apn.pe_w"], x, bias=W["apn.pe_b"], epilogue=EPI_SCALE_RES, gamma=W["apn.ones"],
+                 residual=buf["p_pos"])                                   # proj(x) + bias + pos_embed
+        for i in range(3):
+            q = f"apn{i}."
+            h = ops.layernorm(x, W[q + "norm1_w"], W[q + "norm1_b"], buf["p_h"], eps=1e-5)
+            ops.gemm(h, W[q + "qkv_w"], buf["p_qkv"])
+            ops.attention64_hd(buf["p_qkv"], buf["p_att"], B, 8, 24)
+            ops.gemm(buf["p_att"], W[q + "proj_w"], x, bias=W[q + "proj_b"], epilogue=EPI_SCALE_RES, gamma=W["apn.ones"], residual=x)
+            h = ops.layernorm(x, W[q + "norm2_w"], W[q + "norm2_b"], buf["p_h"], eps=1e-5)
+            ops.gemm(h, W[q + "fc1_w"], buf["p_mlp"], bias=W[q + "fc1_b"], epilogue=EPI_GELU)
+            ops.gemm(buf["p_mlp"], W[q + "fc2_w"], x, bias=W[q + "fc2_b"], epilogue=EPI_SCALE_RES, gamma=W["apn.ones"], residual=x,
+                     prefetch=W["pnp.fc1_w"] if i == 2 else None)
+        ops.layernorm(x, W["apn.norm_w"], W["apn.norm_b"], buf["p_flat"], eps=1e-5)
+        ops.gemm(buf["p_flat"].view(B, 64 * 192), W["pnp.fc1_w"], buf["fc1"], bias=W["pnp.fc1_b"], epilogue=EPI_GELU, prefetch=W["pnp.fc2_w"])
+        ops.gemm(buf["fc1"], W["pnp.fc2_w"], buf["hh"], bias=W["pnp.fc2_b"], epilogue=EPI_GELU, M=B, K=1024, ldx=2048, prefetch=W["pnp.fc2z_w"])
+        ops.gemm(buf["fc1"][:, 1024:], W["pnp.fc2z_w"], buf["hz"], bias=W["pnp.fc2z_b"], epilogue=EPI_GELU, M=B, K=1024, ldx=2048)
         rot_dim, kind, is_allo = ROT_TYPES[cfg.r_type]
         ops.pose_tail_rt(buf["hh"], buf["hz"], 256, W, buf["cam_K"], buf["bbox_center"], buf["resize_ratio"], buf["roi_wh"],
                          cfg.dataset == "wild6d", cfg.t_type == "site", rot_dim, kind, is_allo, buf, B)
@@ -792,7 +843,8 @@ class PoseNet(nn.Module):
 
     @torch.no_grad()
     def run_pnp(self, x_nchw, data, device="cuda", mask=None):
-        """ConvPnPNet.forward (network/conv_pnp_net.py:137-201) on x = cat(coor, roi_coord_2d) (B,5,64,64): returns
+        """ConvPnPNet.forward (network/conv_pnp_net.py:137-201) -- AttentionPnPNet.forward (network/attention_pnp_net.py:119-124) with
+        pnp_head='att' -- on x = cat(coor, roi_coord_2d) (B,5,64,64): returns
         (pred_rot (B,rot_dim), t (B,3)); `data` supplies the camera scalars the fused pose tail also reads.  mask (B,1,64,64):
         the mask_attention input, required when mask_attention_type='mul'."""
         B = x_nchw.shape[0]

@@ -164,6 +164,34 @@ def param_manifest(cfg: PoseNetConfig = PoseNetConfig()):
     m["feat_reducer.weight"] = (256, fc, 1, 1)
     m["feat_reducer.bias"] = (256,)
     _xyz_head_manifest("xyz_deform_head", 512, m)
+    if cfg.pnp_head == "att":
+        # AttentionPnPNet(in_chans=5, embed_dim=192, depth=3, num_heads=8) (network/attention_pnp_net.py:36-77): own Parameter first,
+        # then children in registration order (norm, patch_embed, block, fc1, fc2, fc1_z, fc2_z, fc_z, fc_r, fc_t); fc_r is 6 wide always
+        p = "pnp_net."
+        m[p + "pos_embed"] = (1, 64, 192)
+        m[p + "norm.weight"] = (192,)
+        m[p + "norm.bias"] = (192,)
+        m[p + "patch_embed.proj.weight"] = (192, 5, 8, 8)
+        m[p + "patch_embed.proj.bias"] = (192,)
+        for i in range(3):
+            q = f"{p}block.{i}."
+            m[q + "norm1.weight"] = (192,)
+            m[q + "norm1.bias"] = (192,)
+            m[q + "attn.qkv.weight"] = (576, 192)
+            m[q + "attn.proj.weight"] = (192, 192)
+            m[q + "attn.proj.bias"] = (192,)
+            m[q + "norm2.weight"] = (192,)
+            m[q + "norm2.bias"] = (192,)
+            m[q + "mlp.fc1.weight"] = (768, 192)
+            m[q + "mlp.fc1.bias"] = (768,)
+            m[q + "mlp.fc2.weight"] = (192, 768)
+            m[q + "mlp.fc2.bias"] = (192,)
+        fin = cfg.fc_in_dim      # 12288
+        for n, shp in (("fc1", (1024, fin)), ("fc2", (256, 1024)), ("fc1_z", (1024, fin)), ("fc2_z", (256, 1024)),
+                       ("fc_z", (1, 256)), ("fc_r", (6, 256)), ("fc_t", (2, 256))):
+            m[f"{p}{n}.weight"] = shp
+            m[f"{p}{n}.bias"] = (shp[0],)
+        return m
     for li, i in enumerate((0, 3, 6)):
         m[f"pnp_net.features.{i}.weight"] = (128, 5 if li == 0 else 128, 3, 3)
         m[f"pnp_net.features.{i + 1}.weight"] = (128,)

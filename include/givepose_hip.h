@@ -50,7 +50,7 @@ enum gp_epilogue {
 };
 
 const char* gp_last_error(void);
-#define GP_ABI_VERSION 324 /* 324: + gp_pnp_conv1_masked, gp_pool_mmm, gp_pose_tail_rt; round 6: + gp_dwconv_ln_groups (322), gp_convnext_mlp_pack_w2_s32 / GP_MLP_S32 (323); 321 = round 5: gp_gemm_desc.gn_rows + gp_gemm_gn_rows (321); gp_gemm variants 19-22, gp_convnext_mlp C = 512 (no layout change); 311 = round 4 (+ gp_groupnorm_upsample2x); 310 = round 3 (gp_gemm_desc: split-operand / fp32 residual stream fields); 200 = round 2 */
+#define GP_ABI_VERSION 325 /* 325: + gp_attention64_hd, gp_patchify_pnp, gp_layernorm at non-power-of-two vector counts (C = 192); 324: + gp_pnp_conv1_masked, gp_pool_mmm, gp_pose_tail_rt; round 6: + gp_dwconv_ln_groups (322), gp_convnext_mlp_pack_w2_s32 / GP_MLP_S32 (323); 321 = round 5: gp_gemm_desc.gn_rows + gp_gemm_gn_rows (321); gp_gemm variants 19-22, gp_convnext_mlp C = 512 (no layout change); 311 = round 4 (+ gp_groupnorm_upsample2x); 310 = round 3 (gp_gemm_desc: split-operand / fp32 residual stream fields); 200 = round 2 */
 int gp_version(void);   /* == GP_ABI_VERSION of the header the library was built from */
 /* device properties the host needs: CU count and arch string ("gfx950...") */
 int gp_device_info(int* cu_count, char* arch, int arch_len);
@@ -245,7 +245,8 @@ int gp_dwconv_ln_groups(const void* x, const void* wt, const float* bias, const 
 int gp_dwconv7_raw_stats(const void* x, const void* wt, const float* bias, void* y, float* stats, int B, int H, int W,
                          int C, int dtype, void* stream);
 
-/* row LayerNorm over C (ConvNeXt downsample LayerNorm2d, ViT-block norms); y row stride ldy (0 = C). */
+/* row LayerNorm over C (ConvNeXt downsample LayerNorm2d, ViT-block norms); y row stride ldy (0 = C).  C must be a multiple of
+ * 16 / element size with at most 256 such vectors; a vector count that is no power of two (C = 192) runs a zero-padded lane group. */
 int gp_layernorm(const void* x, const float* w, const float* b, void* y, long rows, int C, float eps, int ldy,
                  int dtype, void* stream);
 
@@ -352,6 +353,13 @@ int gp_patchify_xyz(const float* xyz4, void* out, int B, int R, int P, int dtype
 /* Multi-head self-attention core of timm 0.9.6 vision_transformer.Attention for 64 tokens x head_dim 32: qkv rows
  * (B*64, 3*heads*32) laid out [q|k|v][head][32]; out (B*64, heads*32) = softmax(q k^T / sqrt(32)) v, fp32 math. */
 int gp_attention64(const void* qkv, void* out, int B, int heads, int dtype, void* stream);
+/* The same core at head_dim 24 or 32 (AttentionPnPNet: 192 channels = 8 heads x 24): qkv (B*64, 3*heads*head_dim) laid out
+ * [q|k|v][head][head_dim]; out (B*64, heads*head_dim) = softmax(q k^T * head_dim^-0.5) v, fp32 math.  head_dim 32 is gp_attention64. */
+int gp_attention64_hd(const void* qkv, void* out, int B, int heads, int head_dim, int dtype, void* stream);
+/* AttentionPnPNet front end (network/attention_pnp_net.py:36-124, PatchEmbed :264-302, fed cat(ivfc, roi_coord_2d) at PoseNet.py:196-197):
+ * the PxP patches of the 5-channel PnP input as GEMM rows (B*(R/P)^2, P*P*5) of `dtype`, k = (ky*P+kx)*5 + c; channels 0-2 from the
+ * (B*R*R,4) fp32 coordinate map xyz4, channels 3-4 from the NCHW (B,2,R,R) fp32 coord2d. */
+int gp_patchify_pnp(const float* xyz4, const float* coord2d, void* out, int B, int R, int P, int dtype, void* stream);
 
 /* ResNet stem (network/resnet.py:137-141): Conv2d(3,64,7,s2,p3,bias=False) + eval BatchNorm (folded by the host into
  * w / b) + ReLU on the NCHW fp32 image -> (B,H/2,W/2,64) channels-last.  w: (147, 64) fp32 tap-major, k = c*49+kh*7+kw. */
