@@ -6,6 +6,8 @@ Public surface mirrors the reference for this path:
   dcnv3_backward     the pybind op DCNv3.dcnv3_backward (dcnv3.h:40-59);  DCNv3Function: functions/dcnv3_func.py:25-98
   Scale_net          network/scale_net.py:22-65 (forward(data, device, mode) -> scale (B,)), run before PoseNet by evaluate.py
   PoseNetConfig      the absl FLAGS the path reads (config/config.py)
+  compute_degree_cm_mAP, MapAccumulator, paper_table
+                     evaluation/eval_utils_cass.py:490-820 and the tables evaluate.py:160-280 logs, on the device (evalmap.py)
 """
 from .config import PoseNetConfig  # noqa: F401
 from .posenet import PoseNet  # noqa: F401
@@ -29,4 +31,7 @@ def __getattr__(name):
     if name == "Scale_net":              # network/scale_net.py:22-65
         from .scale_net import Scale_net
         return Scale_net
+    if name in ("compute_degree_cm_mAP", "MapAccumulator", "paper_table"):      # evaluation/eval_utils_cass.py:490
+        from . import evalmap
+        return getattr(evalmap, name)
     raise AttributeError(name)

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # GP_LIB_PATH: A/B runs of two builds on one box (scripts/race_probe.py); the default is the in-tree library
 LIB_PATH = os.environ.get("GP_LIB_PATH") or os.path.join(_HERE, "libgivepose_hip.so")
 
-ABI_VERSION = 325        # include/givepose_hip.h GP_ABI_VERSION: gp_gemm_desc layout (checked against gp_version() at load)
+ABI_VERSION = 326       # include/givepose_hip.h GP_ABI_VERSION: gp_gemm_desc layout (checked against gp_version() at load)
 GP_F32, GP_F16, GP_F64 = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_LRELU = 0, 1, 2, 3
 EPI_NONE, EPI_GELU, EPI_RELU, EPI_LRELU, EPI_SCALE_RES, EPI_RES_RELU, EPI_LNFOLD_GELU = 0, 1, 2, 3, 4, 5, 6
@@ -87,6 +87,10 @@ PROTOTYPES = {
     "gp_sn_avgpool": ([_P] * 2 + [c_int] * 3 + [_P], c_int),
     "gp_sn_se": ([_P] * 6 + [c_int] * 3 + [_P], c_int),
     "gp_sn_head": ([_P] * 12 + [c_int] * 5 + [_P], c_int),
+    "gp_eval_normalise": ([_P, c_int, _P, c_long, _P], c_int),
+    "gp_eval_pair_overlaps": ([_P, _P, c_int, _P, _P, c_int] + [_P] * 6 + [c_long, _P], c_int),
+    "gp_eval_match": ([_P] * 5 + [c_int, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_long, c_long] + [_P] * 6, c_int),
+    "gp_eval_ap": ([_P, _P, c_long, _P, _P, _P, c_int, c_int, _P, c_long, c_int, c_int, _P, _P], c_int),
     "gp_graph_begin": ([_P], c_int),
     "gp_graph_end": ([_P, POINTER(c_void_p)], c_int),
     "gp_graph_launch": ([_P, _P], c_int),

@@ -360,3 +360,76 @@ def synth_scale_batch(B, seed=0, img_size=256):
     cat = r.integers(0, 6, B)
     d["one_hot"] = np.eye(6, dtype=np.float32)[cat]
     return d
+
+
+# ------------------------------------------------------------------------------------------ synthetic evaluation results
+NOCS_SYNSET = ["BG", "bottle", "bowl", "camera", "can", "laptop", "mug"]      # evaluate.py:153
+
+
+def _rot_axis_angle(axis, angle):
+    x, y, z = axis / np.linalg.norm(axis)
+    c, s, C = np.cos(angle), np.sin(angle), 1 - np.cos(angle)
+    return np.array([[x * x * C + c, x * y * C - z * s, x * z * C + y * s], [y * x * C + z * s, y * y * C + c, y * z * C - x * s],
+                     [z * x * C - y * s, z * y * C + x * s, z * z * C + c]])
+
+
+def synth_eval_frame(seed, frame, attempt=0, gt_without=(), pred_without=()):
+    """One seeded frame of evaluation input in the reference's `final_results` layout (evaluate.py:94-133; float64 arrays): 3-6 ground
+    truths of random NOCS classes (several of one class happen), predictions = ground truths perturbed by a few degrees / centimetres /
+    per cent of scale (a tenth of them far off), some missed, some relabelled to another class, plus false positives.  About one frame
+    in 12 has no prediction, no ground truth or neither.  gt_without / pred_without: class ids that never occur as ground truth /
+    prediction.  Scores are distinct inside the frame; `synth_eval_results` makes them distinct over the run."""
+    rng = np.random.default_rng([seed, frame, attempt])
+    gt_classes = [c for c in range(1, 7) if c not in gt_without]
+    pred_classes = [c for c in range(1, 7) if c not in pred_without]
+    kind = rng.random()
+    n_gt = 0 if kind < 0.05 else int(rng.integers(3, 7))
+    g_cls = rng.choice(gt_classes, n_gt).astype(np.int32)
+    g_rt, g_sz, g_hv = np.zeros((n_gt, 4, 4)), np.zeros((n_gt, 3)), np.ones(n_gt, np.int32)
+    p_rt, p_sz, p_cls = [], [], []
+    for k in range(n_gt):
+        R = _rot_axis_angle(rng.standard_normal(3), rng.uniform(0, np.pi))
+        s = rng.uniform(0.15, 0.4)
+        g_rt[k, :3, :3], g_rt[k, :3, 3], g_rt[k, 3, 3] = s * R, [rng.uniform(-0.3, 0.3), rng.uniform(-0.3, 0.3), rng.uniform(0.6, 1.5)], 1
+        size = MEAN_SIZES[g_cls[k] - 1].astype(np.float64) * rng.uniform(0.9, 1.1, 3)
+        g_sz[k] = size / np.linalg.norm(size)
+        if g_cls[k] == 6:
+            g_hv[k] = int(rng.integers(0, 2))
+        if rng.random() < 0.1 or 0.05 <= kind < 0.085:      # missed (or a frame without any prediction)
+            continue
+        far = rng.random() < 0.1
+        Rp = R @ _rot_axis_angle(rng.standard_normal(3), np.deg2rad(rng.uniform(0, 180) if far else rng.uniform(0.05, 15)))
+        if NOCS_SYNSET[g_cls[k]] in ("bottle", "bowl", "can", "mug") and rng.random() < 0.5:
+            Rp = Rp @ _rot_axis_angle(np.array([0.0, 1.0, 0.0]), rng.uniform(0, 2 * np.pi))
+        M = np.eye(4)
+        M[:3, :3] = s * (1 + rng.uniform(-0.15, 0.15)) * Rp
+        M[:3, 3] = g_rt[k, :3, 3] + rng.standard_normal(3) * (0.10 if far else 0.025)
+        c = int(g_cls[k])
+        if rng.random() < 0.07 and len(pred_classes) > 1:
+            c = int(rng.choice([q for q in pred_classes if q != c]))
+        if c in pred_without:
+            continue
+        p_rt.append(M); p_sz.append(g_sz[k] * rng.uniform(0.9, 1.1, 3)); p_cls.append(c)
+    for _ in range(int(rng.random() < 0.25) if kind >= 0.085 or kind < 0.02 else 0):      # a false positive
+        M = np.eye(4)
+        M[:3, :3] = rng.uniform(0.15, 0.4) * _rot_axis_angle(rng.standard_normal(3), rng.uniform(0, np.pi))
+        M[:3, 3] = [rng.uniform(-0.3, 0.3), rng.uniform(-0.3, 0.3), rng.uniform(0.6, 1.5)]
+        size = rng.uniform(0.2, 1.0, 3)
+        p_rt.append(M); p_sz.append(size / np.linalg.norm(size)); p_cls.append(int(rng.choice(pred_classes)))
+    n = len(p_cls)
+    scores = (rng.permutation(n) + rng.uniform(0.05, 0.95, n)) / max(n, 1)
+    return dict(gt_class_ids=g_cls, gt_RTs=g_rt, gt_scales=g_sz, gt_handle_visibility=g_hv,
+                pred_bboxes=np.tile(np.array([[10, 20, 110, 140]], np.int32), (n, 1)).reshape(n, 4),
+                pred_class_ids=np.asarray(p_cls, np.int32), pred_scales=np.asarray(p_sz, np.float64).reshape(n, 3),
+                pred_scores=scores, pred_RTs=np.asarray(p_rt, np.float64).reshape(n, 4, 4))
+
+
+def synth_eval_results(n_frames, seed, attempts=None, **kw):
+    """`n_frames` seeded frames (synth_eval_frame); the scores are made distinct over the whole run (each frame's lie in a slot of their
+    own of width 1 / n_frames).  attempts: {frame: attempt} for the frames a fixture generator drew again."""
+    out = []
+    for f in range(n_frames):
+        r = synth_eval_frame(seed, f, (attempts or {}).get(f, 0), **kw)
+        r["pred_scores"] = (r["pred_scores"] + (f * 7919) % n_frames) / n_frames
+        out.append(r)
+    return out

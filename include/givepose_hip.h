@@ -50,7 +50,7 @@ enum gp_epilogue {
 };
 
 const char* gp_last_error(void);
-#define GP_ABI_VERSION 325 /* 325: + gp_attention64_hd, gp_patchify_pnp, gp_layernorm at non-power-of-two vector counts (C = 192); 324: + gp_pnp_conv1_masked, gp_pool_mmm, gp_pose_tail_rt; round 6: + gp_dwconv_ln_groups (322), gp_convnext_mlp_pack_w2_s32 / GP_MLP_S32 (323); 321 = round 5: gp_gemm_desc.gn_rows + gp_gemm_gn_rows (321); gp_gemm variants 19-22, gp_convnext_mlp C = 512 (no layout change); 311 = round 4 (+ gp_groupnorm_upsample2x); 310 = round 3 (gp_gemm_desc: split-operand / fp32 residual stream fields); 200 = round 2 */
+#define GP_ABI_VERSION 326 /* 326: + gp_eval_normalise, gp_eval_pair_overlaps, gp_eval_match, gp_eval_ap (degree-cm / 3D-IoU mAP on the device); 325: + gp_attention64_hd, gp_patchify_pnp, gp_layernorm at non-power-of-two vector counts (C = 192); 324: + gp_pnp_conv1_masked, gp_pool_mmm, gp_pose_tail_rt; round 6: + gp_dwconv_ln_groups (322), gp_convnext_mlp_pack_w2_s32 / GP_MLP_S32 (323); 321 = round 5: gp_gemm_desc.gn_rows + gp_gemm_gn_rows (321); gp_gemm variants 19-22, gp_convnext_mlp C = 512 (no layout change); 311 = round 4 (+ gp_groupnorm_upsample2x); 310 = round 3 (gp_gemm_desc: split-operand / fp32 residual stream fields); 200 = round 2 */
 int gp_version(void);   /* == GP_ABI_VERSION of the header the library was built from */
 /* device properties the host needs: CU count and arch string ("gfx950...") */
 int gp_device_info(int* cu_count, char* arch, int arch_len);
@@ -422,6 +422,43 @@ int gp_sn_se(const float* pooled, const float* w1, const float* b1, const float*
 int gp_sn_head(const float* feat_roi, const float* feat_full, const float* one_hot, const float* roi_wh, const float* mean_size,
                const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, float* scale,
                int B, int F, int feat_dim, int cats_num, int use_hw, void* stream);
+
+/* ---- degree-cm / 3D-IoU mAP evaluation (evaluation/eval_utils_cass.py:490-820 of the reference), float64 arithmetic on the device.
+ * Poses (n,4,4) and sizes (n,3) are row-major GP_F32 or GP_F64 and are widened to float64 (exact).  The caller groups the run:
+ * a GROUP is one (frame, class) that has a prediction or a ground truth; the predictions of group g occupy the SLOTS
+ * [pred_off[g], pred_off[g+1]) in descending score order, its ground truths the slots [gt_off[g], gt_off[g+1]), and its pairs the
+ * entries pair_off[g] + i * n_gt(g) + j of the pair arrays.  A group may hold at most GP_EVAL_MAX_PER_GROUP of either. */
+#define GP_EVAL_MAX_PER_GROUP 64
+/* out (n,4,4) float64 = rt with rows 0..2 divided by cbrt(det rt[:3,:3]) (evaluate.py:215-227: the scale-normalised view). */
+int gp_eval_normalise(const void* rt, int dtype, double* out, long n, void* stream);
+/* Per pair p = (row pair_pred[p] of the prediction arrays, row pair_gt[p] of the ground-truth arrays), pair_sym[p] != 0 for the
+ * classes symmetric about y (bottle / bowl / can, mug with an invisible handle): iou[p] = float32 of compute_3d_iou_new
+ * (real_iou form: axis-aligned boxes of the transformed corners; symmetric: max over RT_1 @ Ry(2 pi i / 20) from 0), and
+ * deg_cm[2p], deg_cm[2p+1] = compute_RT_degree_cm_symmetry (NaN from an arccos argument outside [-1, 1] propagates).
+ * cs20: cos(2 pi i / 20) for i < 20, then sin(2 pi i / 20), as the host computes them. */
+int gp_eval_pair_overlaps(const void* pred_rt, const void* pred_size, int pred_dtype, const void* gt_rt, const void* gt_size,
+                          int gt_dtype, const int* pair_pred, const int* pair_gt, const unsigned char* pair_sym,
+                          const double* cs20, float* iou, double* deg_cm, long n_pairs, void* stream);
+/* Greedy matching per (group, threshold cell).  IoU cells (compute_3d_matches:303-331): iou_pred_flag (n_iou, n_pred) and
+ * iou_gt_flag (n_iou, n_gt), one byte per slot, 1 = matched.  Pose cells (compute_match_from_degree_cm:462-485), cell = d * n_shift
+ * + s: pose_pred_flag (n_deg * n_shift, n_pred), pose_gt_flag (n_deg * n_shift, n_gt); with pose_iou_cell >= 0 only the
+ * predictions matched in that IoU cell enter (use_matches_for_pose), the others get flag 0.  max_per_group is the caller's
+ * largest group (GP_ERR_INVALID above GP_EVAL_MAX_PER_GROUP); a group that exceeds the limit all the same is skipped and
+ * status[0] (device int, zeroed by the caller) is set to 1. */
+int gp_eval_match(const float* iou, const double* deg_cm, const int* pred_off, const int* gt_off, const int* pair_off, int n_groups,
+                  int max_per_group, const double* iou_thr, int n_iou, const double* deg_thr, int n_deg, const double* shift_thr,
+                  int n_shift, int pose_iou_cell, long n_pred, long n_gt, unsigned char* iou_pred_flag,
+                  unsigned char* iou_gt_flag, unsigned char* pose_pred_flag, unsigned char* pose_gt_flag, int* status, void* stream);
+/* AP per (class, cell) (compute_ap_from_matches_scores:336-362) and the mean over the classes.  flags (n_cells, n_pred) from
+ * gp_eval_match; valid (n_pred bytes) or NULL: only slots with valid != 0 take part (the IoU flag row of use_matches_for_pose);
+ * order: the slots class-major, inside a class in descending score order over the whole run, class c at [cls_off[c],
+ * cls_off[c+1]); cls_ngt[c] the class's ground-truth count (below 2^22).  The sum over the recall steps is taken in the order of
+ * numpy's pairwise summation, so the result is the reference's bit for bit when the match flags are.  work: n_workgroups *
+ * work_stride doubles, work_stride > the longest class.  ap (n_cls + 1, n_cells): the classes, then their mean (pairwise_mean != 0:
+ * the 8-accumulator order numpy uses for a strided 1-D mean of 8 or more classes; n_cls <= 128). */
+int gp_eval_ap(const unsigned char* flags, const unsigned char* valid, long n_pred, const int* order, const int* cls_off,
+               const int* cls_ngt, int n_cls, int n_cells, double* work, long work_stride, int n_workgroups, int pairwise_mean,
+               double* ap, void* stream);
 
 /* ---- per-launch HIP-event timing (bench.py roofline leg).  Between begin/end every gp_* launch on
  * `stream` is bracketed by hipEvents; gp_timing_report fills, per kernel class (GP_KC_*), launches,
