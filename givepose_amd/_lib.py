@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # GP_LIB_PATH: A/B runs of two builds on one box (scripts/race_probe.py); the default is the in-tree library
 LIB_PATH = os.environ.get("GP_LIB_PATH") or os.path.join(_HERE, "libgivepose_hip.so")
 
-ABI_VERSION = 326       # include/givepose_hip.h GP_ABI_VERSION: gp_gemm_desc layout (checked against gp_version() at load)
+ABI_VERSION = 327       # include/givepose_hip.h GP_ABI_VERSION: gp_gemm_desc layout (checked against gp_version() at load)
 GP_F32, GP_F16, GP_F64 = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_LRELU = 0, 1, 2, 3
 EPI_NONE, EPI_GELU, EPI_RELU, EPI_LRELU, EPI_SCALE_RES, EPI_RES_RELU, EPI_LNFOLD_GELU = 0, 1, 2, 3, 4, 5, 6
@@ -64,6 +64,7 @@ PROTOTYPES = {
     "gp_deconv_col2im": ([_P, _P] + [c_int] * 5 + [_P], c_int),
     "gp_xyz_out_layer": ([_P] * 5 + [c_int] * 4 + [_P], c_int),
     "gp_pointwise_k3": ([_P] * 4 + [c_long, c_int, c_int, _P], c_int),
+    "gp_dcnv3_xyz_project": ([_P] * 6 + [c_long] + [c_int] * 14 + [_P], c_int),
     "gp_pnp_conv1": ([_P] * 4 + [c_int] * 4 + [_P], c_int),
     "gp_xyz_conv3x3_s2": ([_P] * 3 + [c_int] * 4 + [_P], c_int),
     "gp_size_head": ([_P] * 8 + [c_int] * 5 + [_P], c_int),

@@ -14,6 +14,8 @@
 //    row with wave shuffles (no memory traffic) and every corner fetch is one fully coalesced
 //    128-B (f16) / 256-B (f32) row segment per group.
 //  * dcnv3_generic_kernel: any G, D % 4 == 0, any K: one thread per (pixel, group, 4 channels).
+// dcnv3_wave8_kernel (further down) is the fp16 form of the first on 16-byte loads; dcnv3_xyz_project_kernel (end of the file) is the whole
+// first encoder layer -- projections folded around the gather of the 3-channel map -- as one launch.
 #include "common.hpp"
 
 namespace {
@@ -510,7 +512,187 @@ template <typename T, typename OT> int launch(const DcnKP& p, hipStream_t s) {
     return 0;
 }
 
+// ---------------------------------------------------------------------------- encoder layer 0: gather of the 3-channel map, then ONE projection
+// The first DCNv3_C layer reads the 3-channel coordinate map.  conv1x1, input_proj, the bilinear samples, the mask-weighted sum over the taps and
+// output_proj are all linear in the sampled value, and a corner outside the map contributes zero, so
+//     out[p, :] = sum_g M_g . [S_g[p]; T_g[p]] + b,    S_g = sum_k m_k bilinear(xyz, p + delta_k)  (3 values),  T_g = the same gather of a constant 1,
+// with M = (256 x 16) folded at pack time: 16 gathered numbers per output pixel instead of a 256-channel map at full resolution, its gather and a
+// K = 256 GEMM.  One crop's map is 64 KB and sits in LDS whole, so every corner is one 16-byte LDS read.
+//  * a workgroup = WAVES chunks of 32 consecutive output pixels of ONE crop (1024 % (32 WAVES) == 0); every wave owns one chunk from end to end;
+//  * gather: a wave iteration is one pixel, a 16-lane row one group, lane t < 9 of a row tap t -- the owner block of dcnv3_wave8_kernel (same addressing,
+//    tap order, range test, zero corner weight, fp32 softmax) on four fp32 channels [x, y, z, 1]; the nine taps are added by a row butterfly;
+//  * projection: lane = 4 output channels, its 4 x 16 block of M in registers, the pixel's 16 numbers broadcast from LDS; fp32 FMAs, one rounding at the store;
+//  * GroupNorm statistics of the fp32 values per chunk (= 32 rows) and 8-channel group, in the layout of gp_gemm's gn epilogue.
+struct XyzKP {
+    const f32x4* xyz;
+    const float* om;
+    const float* m;
+    const float* bias;
+    void* out;
+    float* gn;
+    long rows;
+    int om_ld, mask_col, logits;
+};
+
+template <typename T, int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void dcnv3_xyz_project_kernel(const XyzKP p) {
+    constexpr int NT = WAVES * 64, PX = WAVES * 32, H = 64, W = 64, U = 4;
+    __shared__ __attribute__((aligned(16))) f32x4 map_s[H * W];
+    __shared__ __attribute__((aligned(16))) f32x4 v_s[PX * 4];          // [pixel][group] = (Sx, Sy, Sz, T)
+    const int lane = threadIdx.x & 63, t = lane & 15, g = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long pb = (long)blockIdx.x * PX;                               // first output pixel of the workgroup (its first chunk is always inside `rows`)
+    const int crop = (int)(pb >> 10);
+    const long r0 = pb + wave * 32;                                      // first output pixel of this wave's chunk
+    const bool live = r0 < p.rows;                                       // wave-uniform (rows % 32 == 0)
+    {
+        const f32x4* src = p.xyz + (long)crop * (H * W);
+#pragma unroll 8
+        for (int i = 0; i < H * W / NT; ++i) map_s[i * NT + threadIdx.x] = src[i * NT + threadIdx.x];
+    }
+    // offsets / logits of U pixels at a time, the next U in flight while these are worked on
+    const bool own = t < 9 && live;
+    const float* omp = p.om + r0 * p.om_ld + (g * 9 + t) * 2;
+    const float* mkp = p.om + r0 * p.om_ld + p.mask_col + g * 9 + t;
+    f32x2 o_n[U];
+    float m_n[U];
+    auto fetch = [&](int it0) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            o_n[u] = f32x2{0.f, 0.f};
+            m_n[u] = p.logits ? -INFINITY : 0.f;
+            if (own) {
+                o_n[u] = *reinterpret_cast<const f32x2*>(omp + (long)(it0 + u) * p.om_ld);
+                m_n[u] = mkp[(long)(it0 + u) * p.om_ld];
+            }
+        }
+    };
+    fetch(0);
+    __syncthreads();
+    const int ti = t / 3, tj = t - ti * 3;                               // tap order: kernel_w outer, kernel_h inner
+    const float os = 1.f, Hf = (float)H, Wf = (float)W;
+#pragma unroll 1
+    for (int it0 = 0; it0 < 32; it0 += U) {
+        f32x2 o_c[U];
+        float m_c[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) { o_c[u] = o_n[u]; m_c[u] = m_n[u]; }
+        if (it0 + U < 32) fetch(it0 + U);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int pl = (int)(r0 & 1023) + it0 + u;                   // pixel inside the crop
+            const int ho = pl >> 5, wo = pl & 31;
+            const float ow = o_c[u][0], oh = o_c[u][1];
+            float m = m_c[u];
+            if (p.logits) {
+                const float mx = group_max(m, 16);
+                const float e = t < 9 ? expf(m - mx) : 0.f;
+                const float sm = group_sum(e, 16);
+                m = e / sm;
+            }
+            const float p0_w_ = (float)(1 - 1 + wo * 2) - 1 * os;
+            const float p0_h_ = (float)(1 - 1 + ho * 2) - 1 * os;
+            float loc_w = p0_w_ + (ti * 1 + ow) * os;
+            float loc_h = p0_h_ + (tj * 1 + oh) * os;
+            const bool in = t < 9 && loc_h > -1.f && loc_w > -1.f && loc_h < Hf && loc_w < Wf;
+            loc_w = in ? loc_w : 0.f;
+            loc_h = in ? loc_h : 0.f;
+            m = in ? m : 0.f;
+            const float fh = floorf(loc_h), fw = floorf(loc_w);
+            const float lh = loc_h - fh, lw = loc_w - fw, hh = 1.f - lh, hw = 1.f - lw;
+            const int h_low = (int)fh, w_low = (int)fw, h_high = h_low + 1, w_high = w_low + 1;
+            const bool hl = h_low >= 0, hhi = h_high <= H - 1, wl = w_low >= 0, whi = w_high <= W - 1;
+            const float w1 = (hl && wl) ? hh * hw : 0.f, w2 = (hl && whi) ? hh * lw : 0.f;
+            const float w3 = (hhi && wl) ? lh * hw : 0.f, w4 = (hhi && whi) ? lh * lw : 0.f;
+            const int y0 = max(h_low, 0), y1 = min(h_high, H - 1), x0 = max(w_low, 0), x1 = min(w_high, W - 1);   // clamped: every index is inside map_s
+            const f32x4 v1 = map_s[y0 * W + x0], v2 = map_s[y0 * W + x1], v3 = map_s[y1 * W + x0], v4 = map_s[y1 * W + x1];
+            f32x4 s;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                float tt = w1 * v1[c];
+                tt = fmaf(w2, v2[c], tt);
+                tt = fmaf(w3, v3[c], tt);
+                tt = fmaf(w4, v4[c], tt);
+                s[c] = group_sum(tt * m, 16);
+            }
+            s[3] = group_sum((((w1 + w2) + w3) + w4) * m, 16);           // the constant-1 channel: what the folded biases are multiplied by
+            if (t == 0) v_s[(wave * 32 + it0 + u) * 4 + g] = s;
+        }
+    }
+    __syncthreads();
+    if (!live) return;
+    f32x4 mr[4][4];                                                      // rows lane*4 .. +3 of M, 16 columns each
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) mr[c][k] = *reinterpret_cast<const f32x4*>(p.m + (lane * 4 + c) * 16 + k * 4);
+    const f32x4 b4 = *reinterpret_cast<const f32x4*>(p.bias + lane * 4);
+    float gs = 0.f, gq = 0.f;
+    T* op = reinterpret_cast<T*>(p.out) + r0 * 256 + lane * 4;
+#pragma unroll 2
+    for (int px = 0; px < 32; ++px) {
+        const f32x4* vp = v_s + (wave * 32 + px) * 4;
+        f32x4 a[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) a[k] = vp[k];
+        float acc[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            float x = b4[c];
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) x = fmaf(mr[c][k][j], a[k][j], x);
+            acc[c] = x;
+        }
+        gs += (acc[0] + acc[1]) + (acc[2] + acc[3]);
+        gq += (acc[0] * acc[0] + acc[1] * acc[1]) + (acc[2] * acc[2] + acc[3] * acc[3]);
+        st4(op + (long)px * 256, acc);
+    }
+    gs = group_sum(gs, 2);
+    gq = group_sum(gq, 2);
+    if ((lane & 1) == 0)    // partial[((crop * chunks + chunk) * 32 + group) * 2], chunks = 1024 / 32
+        *reinterpret_cast<f32x2*>(p.gn + ((r0 >> 5) * 32 + (lane >> 1)) * 2) = f32x2{gs, gq};
+}
+
 }  // namespace
+
+/* see include/givepose_hip.h */
+extern "C" int gp_dcnv3_xyz_project(const float* xyz4, const float* om, const float* m, const float* bias, void* out, float* gn_partial,
+                                    long rows, int H, int W, int K, int stride, int pad, int dil, int G, int om_ld, int mask_col,
+                                    int mask_is_logits, int gn_groups, int gn_hw, int gn_rows, int dtype, void* stream) {
+    GP_REQUIRE(xyz4 && om && m && bias && out && gn_partial, "gp_dcnv3_xyz_project: null pointer");
+    GP_REQUIRE(H == 64 && W == 64 && K == 3 && stride == 2 && pad == 1 && dil == 1 && G == 4,
+               "gp_dcnv3_xyz_project: geometry %dx%d K%d s%d p%d d%d G%d is not the encoder's (64x64 K3 s2 p1 d1 G4)", H, W, K, stride, pad, dil, G);
+    GP_REQUIRE(rows > 0 && rows % 32 == 0, "gp_dcnv3_xyz_project: rows=%ld must be a positive multiple of 32", rows);
+    GP_REQUIRE(dtype == GP_F32 || dtype == GP_F16, "gp_dcnv3_xyz_project: bad dtype");
+    GP_REQUIRE(mask_col >= 72 && om_ld >= mask_col + 36 && om_ld % 2 == 0, "gp_dcnv3_xyz_project: om_ld=%d mask_col=%d", om_ld, mask_col);
+    GP_REQUIRE(gn_groups == 32 && gn_hw == 1024 && gn_rows == 32, "gp_dcnv3_xyz_project: GroupNorm statistics come per 32 rows of 32 groups of a 32x32 map (gn_groups=%d gn_hw=%d gn_rows=%d)",
+               gn_groups, gn_hw, gn_rows);
+    GP_REQUIRE(((uintptr_t)xyz4 | (uintptr_t)out | (uintptr_t)m | (uintptr_t)bias) % 16 == 0 && ((uintptr_t)om | (uintptr_t)gn_partial) % 8 == 0,
+               "gp_dcnv3_xyz_project: misaligned pointer");
+    XyzKP p;
+    p.xyz = reinterpret_cast<const f32x4*>(xyz4); p.om = om; p.m = m; p.bias = bias; p.out = out; p.gn = gn_partial;
+    p.rows = rows; p.om_ld = om_ld; p.mask_col = mask_col; p.logits = mask_is_logits ? 1 : 0;
+    hipStream_t s = (hipStream_t)stream;
+    const int esz = dtype == GP_F16 ? 2 : 4;
+    const double crops = (double)((rows + 1023) / 1024);
+    // algorithmic bytes of THIS formulation: the map once + the consumed offsets / logits + the output; FLOPs: 36 taps x 4 corners x 4 channels + the 256 x 16 projection
+    gp_timing_before(s, GP_KC_DCNV3, (double)rows * (36 * 4 * 4 * 2.0 + 256 * 16 * 2.0), crops * H * W * 16 + (double)rows * 108 * 4 + (double)rows * 256 * esz);
+    gp_timing_label("dcnv3_xyz_project rows%ld", rows);
+    // few crops: 64 pixels per workgroup (16 workgroups per crop); otherwise 256 (two workgroups of 8 waves fit a CU's LDS)
+    const bool big = rows >= 32 * 1024;
+    const long grid = (rows + (big ? 256 : 64) - 1) / (big ? 256 : 64);
+    GP_REQUIRE(grid < (1l << 31), "gp_dcnv3_xyz_project: grid too large");
+    if (dtype == GP_F16) {
+        if (big) hipLaunchKernelGGL((dcnv3_xyz_project_kernel<half_t, 8>), dim3((unsigned)grid), dim3(512), 0, s, p);
+        else hipLaunchKernelGGL((dcnv3_xyz_project_kernel<half_t, 2>), dim3((unsigned)grid), dim3(128), 0, s, p);
+    } else {
+        if (big) hipLaunchKernelGGL((dcnv3_xyz_project_kernel<float, 8>), dim3((unsigned)grid), dim3(512), 0, s, p);
+        else hipLaunchKernelGGL((dcnv3_xyz_project_kernel<float, 2>), dim3((unsigned)grid), dim3(128), 0, s, p);
+    }
+    GP_LAUNCH_CHECK("gp_dcnv3_xyz_project");
+}
 
 extern "C" int gp_dcnv3_forward(const void* in, const void* offset, const void* mask, void* out, int N, int H,
                                 int W, int G, int D, int K, int stride, int pad, int dil, float offset_scale,

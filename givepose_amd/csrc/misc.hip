@@ -1161,6 +1161,7 @@ extern "C" int gp_pointwise_k3(const float* xyz4, const float* w, const float* b
     hipStream_t s = (hipStream_t)stream;
     const long total = cdiv(rows, (256 / (Cout / vec)) * 8) * 256;
     gp_timing_before(s, GP_KC_ELEMENTWISE, 6.0 * rows * Cout, rows * 16.0 + (double)rows * Cout * esz);
+    gp_timing_label("pointwise_k3 rows%ld Cout%d", rows, Cout);
     if (dtype == GP_F16) hipLaunchKernelGGL(pointwise_k3_kernel<half_t>, dim3(cdiv(total, 256)), dim3(256), 0, s, xyz4, w, b, (half_t*)y, rows, Cout);
     else hipLaunchKernelGGL(pointwise_k3_kernel<float>, dim3(cdiv(total, 256)), dim3(256), 0, s, xyz4, w, b, (float*)y, rows, Cout);
     GP_LAUNCH_CHECK("gp_pointwise_k3");

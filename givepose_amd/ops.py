@@ -13,7 +13,7 @@ from . import _lib
 from ._lib import (ACT_GELU, ACT_LRELU, ACT_NONE, ACT_RELU, EPI_GELU, EPI_LNFOLD_GELU, EPI_LRELU, EPI_NONE, EPI_RELU, EPI_RES_RELU,
                    EPI_SCALE_RES, GP_F16, GP_F32, GP_F64, GemmDesc, check)
 
-__all__ = ["dtype_code", "gemm", "conv2d_nhwc", "dcnv3_forward", "dcnv3_backward", "dcnv3_forward_into", "convnext_stem", "dwconv_ln",
+__all__ = ["dtype_code", "gemm", "conv2d_nhwc", "dcnv3_forward", "dcnv3_backward", "dcnv3_forward_into", "dcnv3_xyz_project", "convnext_stem", "dwconv_ln",
            "layernorm", "groupnorm", "upsample_bilinear2x", "deconv_col2im", "xyz_out_layer", "pointwise_k3",
            "pnp_conv1", "pnp_conv1_masked", "pool_mmm", "xyz_conv3x3_s2", "size_head", "pose_tail", "pose_tail_rt", "mask_resize_nearest"]
 
@@ -535,6 +535,23 @@ def pointwise_k3(xyz4, w, b, out):
     rows = xyz4.shape[0]
     check(_L().gp_pointwise_k3(_ptr(xyz4), _ptr(w), _ptr(b), _ptr(out), rows, w.shape[0], dtype_code(out.dtype), _stream()),
           "gp_pointwise_k3")
+    return out
+
+
+def dcnv3_xyz_project(xyz4, om, m, bias, out, gn, mask_col=72, mask_is_logits=True):
+    """gp_dcnv3_xyz_project: the first MAPEncoder layer behind its offset / mask branch.  xyz4 (crops*4096, 4) fp32, om (rows, om_ld) fp32
+    [offsets | mask logits], m (256, 16) / bias (256,) fp32 (posenet.enc0_xyz_pack), out (rows, 256); gn = (partial, 32, 1024, 32)."""
+    _contig(_chk(xyz4, "xyz4"), "xyz4"), _contig(_chk(om, "om"), "om"), _contig(_chk(out, "out"), "out")
+    rows = out.shape[0]
+    if xyz4.dtype != torch.float32 or om.dtype != torch.float32 or m.dtype != torch.float32 or bias.dtype != torch.float32:
+        raise TypeError("dcnv3_xyz_project: xyz4, om, m and bias are float32")
+    if tuple(m.shape) != (256, 16) or bias.numel() != 256 or out.shape[1] != 256 or om.shape[0] < rows or xyz4.shape[0] < (rows + 1023) // 1024 * 4096:
+        raise RuntimeError("dcnv3_xyz_project: shapes")
+    if gn[0].numel() < (rows + 1023) // 1024 * 32 * 32 * 2:
+        raise RuntimeError("dcnv3_xyz_project: the gn_partial buffer is too small for 32 chunks of 32 groups per crop")
+    check(_L().gp_dcnv3_xyz_project(_ptr(xyz4), _ptr(om), _ptr(_contig(m, "m")), _ptr(bias), _ptr(out), _ptr(gn[0]), rows, 64, 64, 3, 2, 1, 1, 4,
+                                    om.shape[1], mask_col, 1 if mask_is_logits else 0, gn[1], gn[2], gn[3], dtype_code(out.dtype), _stream()),
+          "gp_dcnv3_xyz_project")
     return out
 
 

@@ -26,6 +26,23 @@ from .config import FLAT_OPS, ROT_TYPES, PoseNetConfig, validate
 OM_LD = 128     # row length of the DCNv3 offset | mask projection output (108 used columns)
 
 
+def enc0_xyz_pack(sd, prefix="nocs_encoder.features.0.", dtype=torch.float32):
+    """Reference-layout state dict -> (M (256, 16), b (256,)) fp32 of gp_dcnv3_xyz_project: the first DCNv3_C layer of the MAPEncoder
+    as a gather of 16 numbers per output pixel and one matrix.  conv1x1, input_proj, the bilinear samples, the
+    mask-weighted tap sum and output_proj are linear in the sampled value and a corner outside the map contributes zero, so with
+    S_g = the gather of [x, y, z] and T_g = the same gather of a constant 1 for group g,
+        out = sum_g M_g . [S_g; T_g] + out_b,   M_g = out_w[:, 64g:64g+64] @ [fold_w[64g:64g+64] | fold_b[64g:64g+64]]
+    (fold_w = input_proj.weight @ conv.weight, fold_b = input_proj.weight @ conv.bias + input_proj.bias).  The products are formed in
+    float64 from the unrounded tensors and rounded to `dtype` once (float64: the unrounded matrix, for tests)."""
+    f64 = lambda k: sd[prefix + k].detach().to(device="cpu", dtype=torch.float64)
+    cw, cb = f64("conv.weight").reshape(256, -1), f64("conv.bias")
+    iw, ib = f64("dcnv3.input_proj.weight"), f64("dcnv3.input_proj.bias")
+    ow, ob = f64("dcnv3.output_proj.weight"), f64("dcnv3.output_proj.bias")
+    fold = torch.cat([iw @ cw, (iw @ cb + ib)[:, None]], 1)                                   # (256, 4): [fold_w | fold_b]
+    m = torch.cat([ow[:, 64 * g:64 * g + 64] @ fold[64 * g:64 * g + 64] for g in range(4)], 1)    # (256, 16), column 4 g + c
+    return m.to(dtype).contiguous(), ob.to(dtype).contiguous()
+
+
 class _Node(nn.Module):
     """Container mirroring one level of the reference module tree (names only)."""
 
@@ -245,6 +262,8 @@ class PoseNet(nn.Module):
                 W[q + "fold_w"] = f32(wf) if li == 0 else gw(wf)
                 W[q + "fold_b"] = f32(sd[d + "input_proj.weight"] @ sd[p + "conv.bias"] + sd[d + "input_proj.bias"])
                 W[q + "out_w"], W[q + "out_b"] = gw(sd[d + "output_proj.weight"]), f32(sd[d + "output_proj.bias"])
+                if li == 0 and T == torch.float16 and not self.split_gemm:     # layer 0 as one gather + one 256 x 16 matrix (gp_dcnv3_xyz_project)
+                    W[q + "xyz_m"], W[q + "xyz_b"] = (f32(t) for t in enc0_xyz_pack(sd, p))
             else:
                 cw = sd[p + "weight"]
                 W[q + "conv_w"] = f32(cw.reshape(256, -1).t()) if li == 0 else gw(cw.permute(0, 2, 3, 1).reshape(256, -1))
@@ -358,11 +377,14 @@ class PoseNet(nn.Module):
         buf["nocs_nchw"], buf["nocs_nhwc4"] = f(B, 3, R, R), f(B * R * R, 4)
         buf["ivfc_nchw"], buf["ivfc_nhwc4"] = f(B, 3, R, R), f(B * R * R, 4)
         buf["mask_out"], buf["size"] = f(B, 1, R, R), f(B, 3)
+        # GP_ENC0_XYZ=0 (A/B switch, read here): encoder layer 0 on the three launches of the 256-channel layers instead of gp_dcnv3_xyz_project
+        enc0_xyz = "enc0.xyz_m" in self._packed and os.environ.get("GP_ENC0_XYZ") != "0"
         for li, r in enumerate((64, 32, 16)):
-            buf[f"e_in{li}"], buf[f"e_proj{li}"] = e(B, r, r, 256), e(B, r, r, 256)
-            buf[f"e_x1{li}"] = e(B * r * r // 4, 256)
+            buf[f"e_in{li}"], buf[f"e_x1{li}"] = e(B, r, r, 256), e(B * r * r // 4, 256)
             buf[f"e_om{li}"] = f(B * r * r // 4, OM_LD)
-            buf[f"e_g{li}"], buf[f"e_o{li}"] = e(B, r // 2, r // 2, 256), e(B, r // 2, r // 2, 256)
+            buf[f"e_o{li}"] = e(B, r // 2, r // 2, 256)
+            if li > 0 or not enc0_xyz:      # (the folded layer 0 has neither the projected full-resolution map nor the gathered one)
+                buf[f"e_proj{li}"], buf[f"e_g{li}"] = e(B, r, r, 256), e(B, r // 2, r // 2, 256)
         if cfg.nocsmap_encoder == "att":
             buf["a_patch"], buf["a_x"], buf["a_h"] = e(B * 64, 192), e(B * 64, 256), e(B * 64, 256)
             buf["a_qkv"], buf["a_att"], buf["a_mlp"] = e(B * 64, 768), e(B * 64, 256), e(B * 64, 1024)
@@ -380,7 +402,7 @@ class PoseNet(nn.Module):
             buf["pooled"] = e(B, 128 * FLAT_OPS[cfg.flat_op])
         buf["pred_rot"], buf["pred_t"], buf["rot_allo"], buf["rot_ego"], buf["trans"] = f(B, cfg.rot_dim), f(B, 3), f(B, 9), f(B, 9), f(B, 3)
         buf["rot6d"] = buf["pred_rot"] if cfg.rot_dim == 6 else None
-        plan = {"buf": buf, "graph": None, "warm": False, "ragged": bool(ragged)}
+        plan = {"buf": buf, "graph": None, "warm": False, "ragged": bool(ragged), "enc0_xyz": enc0_xyz}
         if ragged:
             # crop -> first crop of its batch (gp_dwconv_ln_groups); rewritten before every launch, the pointer is what the graph holds.
             # Padding crops (beyond the real ones) are batches of their own and keep benign inputs: zero image, identity camera.
@@ -574,8 +596,15 @@ class PoseNet(nn.Module):
                     q = f"enc{weights_of}."
             if cfg.use_dcn == "dcnv3":
                 xin = buf[f"e_in{li}"]
-                # the full-resolution projection of every crop: one launch over all groups
-                if li == 0:
+                # layer 0 in fp16 mode: only the offset / mask branch below, then ONE launch from the 3-channel map to e_o0 (gp_dcnv3_xyz_project)
+                xyz0 = li == 0 and plan.get("enc0_xyz") and only_layer is None
+                # otherwise the full-resolution projection of every crop: one launch over all groups
+                if xyz0:
+                    # the reference's im2col_step rule (dcnv3_cuda.cu:46-49) is about ONE batch: checked here, per coupling group, as its gather would
+                    nb = B if (plan.get("ragged") or not (self.dcn_couple and B > self.dcn_couple)) else self.dcn_couple
+                    if nb % min(nb, 256):
+                        raise RuntimeError(f"gp_dcnv3_forward: batch({nb}) must divide im2col_step({min(nb, 256)})")
+                elif li == 0:
                     ops.pointwise_k3(buf["nocs_nhwc4"], W[q + "fold_w"], W[q + "fold_b"], buf[f"e_proj{li}"].view(-1, 256))
                 else:
                     ops.gemm(prev.view(-1, 256), W[q + "fold_w"], buf[f"e_proj{li}"].view(-1, 256), bias=W[q + "fold_b"])
@@ -590,8 +619,9 @@ class PoseNet(nn.Module):
                         ops.gemm(prev.view(-1, 256), W[q + "conv_w"], xin.view(-1, 256), bias=W[q + "conv_b"])
                     ops.dwconv_ln_groups(xin, W[q + "dw_w"], W[q + "dw_b"], W[q + "ln_w"], W[q + "ln_b"], buf[f"e_x1{li}"], 3, buf["grp"], act=ACT_GELU)
                     ops.gemm(buf[f"e_x1{li}"], W[q + "om_w"], buf[f"e_om{li}"], bias=W[q + "om_b"])
-                    ops.dcnv3_forward_into(buf[f"e_proj{li}"], buf[f"e_om{li}"], buf[f"e_om{li}"][:, 72:], buf[f"e_g{li}"], 3, 2, 1, 1, 4, 64, 1.0,
-                                           off_ld=OM_LD, mask_ld=OM_LD, mask_is_logits=True)
+                    if not xyz0:
+                        ops.dcnv3_forward_into(buf[f"e_proj{li}"], buf[f"e_om{li}"], buf[f"e_om{li}"][:, 72:], buf[f"e_g{li}"], 3, 2, 1, 1, 4, 64, 1.0,
+                                               off_ld=OM_LD, mask_ld=OM_LD, mask_is_logits=True)
                 # the offset / mask branch and the gather see ONE batch's flat prefix at a time (grouped launches: a group =
                 # one batch of dcn_couple crops; otherwise the whole forward is the one group)
                 Bg = self.dcn_couple if (self.dcn_couple and B > self.dcn_couple) else B
@@ -614,9 +644,16 @@ class PoseNet(nn.Module):
                     om_g = buf[f"e_om{li}"][g0 * r * r // 4:(g0 + Bg) * r * r // 4]
                     ops.dwconv_ln(xin_g, W[q + "dw_w"], W[q + "dw_b"], W[q + "ln_w"], W[q + "ln_b"], x1_g, 3, act=ACT_GELU, n_pixels=nq)
                     ops.gemm(x1_g, W[q + "om_w"], om_g, bias=W[q + "om_b"])
-                    ops.dcnv3_forward_into(buf[f"e_proj{li}"][gs], om_g, om_g[:, 72:], buf[f"e_g{li}"][gs], 3, 2, 1, 1, 4, 64, 1.0,
-                                           off_ld=OM_LD, mask_ld=OM_LD, mask_is_logits=True)
+                    if not xyz0:
+                        ops.dcnv3_forward_into(buf[f"e_proj{li}"][gs], om_g, om_g[:, 72:], buf[f"e_g{li}"][gs], 3, 2, 1, 1, 4, 64, 1.0,
+                                               off_ld=OM_LD, mask_ld=OM_LD, mask_is_logits=True)
                 y = buf[f"e_o{li}"]
+                if xyz0:     # the rows of e_om0 of all groups are contiguous, output row j is global output pixel j: one launch for every crop
+                    ops.dcnv3_xyz_project(buf["nocs_nhwc4"], buf["e_om0"], W[q + "xyz_m"], W[q + "xyz_b"], y.view(-1, 256),
+                                          gn=self._gnarg(buf, ro * ro, 32))
+                    self._gn(y, W[q + "gn_w"], W[q + "gn_b"], ACT_RELU, buf, fused=True, rows=32)
+                    prev = y
+                    continue
                 ops.gemm(buf[f"e_g{li}"].view(-1, 256), W[q + "out_w"], y.view(-1, 256), bias=W[q + "out_b"],
                          gn=self._gnarg(buf, ro * ro))
                 fused = True

@@ -50,7 +50,7 @@ enum gp_epilogue {
 };
 
 const char* gp_last_error(void);
-#define GP_ABI_VERSION 326 /* 326: + gp_eval_normalise, gp_eval_pair_overlaps, gp_eval_match, gp_eval_ap (degree-cm / 3D-IoU mAP on the device); 325: + gp_attention64_hd, gp_patchify_pnp, gp_layernorm at non-power-of-two vector counts (C = 192); 324: + gp_pnp_conv1_masked, gp_pool_mmm, gp_pose_tail_rt; round 6: + gp_dwconv_ln_groups (322), gp_convnext_mlp_pack_w2_s32 / GP_MLP_S32 (323); 321 = round 5: gp_gemm_desc.gn_rows + gp_gemm_gn_rows (321); gp_gemm variants 19-22, gp_convnext_mlp C = 512 (no layout change); 311 = round 4 (+ gp_groupnorm_upsample2x); 310 = round 3 (gp_gemm_desc: split-operand / fp32 residual stream fields); 200 = round 2 */
+#define GP_ABI_VERSION 327 /* 327: + gp_dcnv3_xyz_project (encoder layer 0 as one gather + one projection); 326: + gp_eval_normalise, gp_eval_pair_overlaps, gp_eval_match, gp_eval_ap (degree-cm / 3D-IoU mAP on the device); 325: + gp_attention64_hd, gp_patchify_pnp, gp_layernorm at non-power-of-two vector counts (C = 192); 324: + gp_pnp_conv1_masked, gp_pool_mmm, gp_pose_tail_rt; round 6: + gp_dwconv_ln_groups (322), gp_convnext_mlp_pack_w2_s32 / GP_MLP_S32 (323); 321 = round 5: gp_gemm_desc.gn_rows + gp_gemm_gn_rows (321); gp_gemm variants 19-22, gp_convnext_mlp C = 512 (no layout change); 311 = round 4 (+ gp_groupnorm_upsample2x); 310 = round 3 (gp_gemm_desc: split-operand / fp32 residual stream fields); 200 = round 2 */
 int gp_version(void);   /* == GP_ABI_VERSION of the header the library was built from */
 /* device properties the host needs: CU count and arch string ("gfx950...") */
 int gp_device_info(int* cu_count, char* arch, int arch_len);
@@ -295,6 +295,24 @@ int gp_xyz_out_layer(const void* x, const float* w, const float* b, float* out_n
  * layer, network/dcnv3.py:26,33). w (Cout,3) fp32. */
 int gp_pointwise_k3(const float* xyz4, const float* w, const float* b, void* y, long rows, int Cout,
                     int dtype, void* stream);
+
+/* The whole first DCNv3_C layer of the MAPEncoder behind its offset / mask branch (conv1x1, input_proj, the DCNv3 gather and
+ * output_proj; network/conv_pnp_net.py:254-272, ops_dcnv3/modules/dcnv3.py:318-356) as one launch.  Every step is linear in the
+ * sampled value and a corner outside the map contributes zero, so
+ *     out[p, :] = m . v[p] + bias,   v[p][4 g + c] = sum over the 9 taps k of  mask_k * bilinear([x, y, z, 1], p + delta_k)[c]
+ * for group g = 0..3 (its own offsets and mask), with m (256, 16) fp32 row-major = per group out_w[:, 64g:64g+64] @ [w | b] of the folded
+ * input projection and bias = out_b (givepose_amd/posenet.py: enc0_xyz_pack).
+ *   xyz4: the (crops*64*64, 4) fp32 coordinate map (the 4th value is not read), ceil(rows / 1024) crops of it;
+ *   om:   fp32 rows of om_ld columns, one per output pixel: offsets at (g*9 + k)*2 + {0:w,1:h}, mask (logits when mask_is_logits != 0:
+ *         softmax over the 9 taps in fp32) at mask_col + g*9 + k, exactly as gp_dcnv3_forward reads them;
+ *   out:  (rows, 256) dtype, rows = output pixels (a multiple of 32; row j is global output pixel j, crop j / 1024): one rounding, at the store.
+ *         A row count, not a batch: the reference's im2col_step rule belongs to the caller.
+ *   gn_partial: (sum, sum of squares) of the fp32 values per gn_rows output rows and 8-channel group, in the layout of gp_gemm's
+ *         gn_partial ((crop, gn_hw / gn_rows, gn_groups, 2)); gn_groups = 32, gn_hw = 1024, gn_rows = 32 only.
+ * Geometry: H = W = 64, K 3, stride 2, pad 1, dil 1, G 4 only; anything else is GP_ERR_INVALID. */
+int gp_dcnv3_xyz_project(const float* xyz4, const float* om, const float* m, const float* bias, void* out, float* gn_partial,
+                         long rows, int H, int W, int K, int stride, int pad, int dil, int G, int om_ld, int mask_col,
+                         int mask_is_logits, int gn_groups, int gn_hw, int gn_rows, int dtype, void* stream);
 
 /* ConvPnPNet first conv: Conv2d(5,Cout,3,s2,p1,bias=False) on cat(ivfc (B*HW,4) fp32, roi_coord_2d
  * (B,2,R,R) fp32 NCHW) (network/PoseNet.py:196-197, conv_pnp_net.py:72-83). w (45, Cout) fp32 tap-major, k = ci*9+kh*3+kw.

@@ -36,6 +36,7 @@ ORDER = ["x0", "t0", "x1", "t1", "x2", "t2", "h2", "x3", "t3", "h3", "size", "co
          "feat_cat", "ya16", "yb16", "ya32", "yb32", "ya64", "yb64", "ivfc_nchw", "ivfc_nhwc4", "p0", "p1", "p2", "fc1", "hh", "hz",
          "rot6d", "pred_t", "rot_ego", "trans"]
 ref = []
+ORDER = [k for k in ORDER if k in net._plan(B, dev, 0)["buf"]]      # (a plan on the folded encoder layer 0 has no e_proj0 / e_g0)
 for i in range(NS):
     for _ in range(3):
         net.forward_device(d[i], slot=i)
