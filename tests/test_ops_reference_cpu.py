@@ -140,6 +140,7 @@ S = "tests/test_scalenet_ops_gpu.py::"
 M = "tests/test_misc_ops_conformance.py::"
 E = "tests/test_evalmap_gpu.py::test_kernels_against_reference_fixtures"
 P = "tests/test_pnp_flags_gpu.py::"
+NC = "tests/test_norm_conformance_gpu.py::"
 A = "tests/test_att_pnp_gpu.py::"
 # entry point -> the operator-level test that holds it against a reference of its own operation (never a whole-network test); graph,
 # timing, version and device-info calls -> the test that exercises them
@@ -156,16 +157,16 @@ CLOSURE = {
     "gp_convnext_mlp_pack_w2_s32": H + "test_convnext_mlp_fused_s32_form",
     "gp_convnext_mlp": H + "test_convnext_mlp_fused",
     "gp_convnext_stem": H + "test_stem",
-    "gp_dwconv_ln": H + "test_dwconv_ln",
+    "gp_dwconv_ln": NC + "test_dwconv_ln",
     "gp_dwconv_ln_groups": M + "test_dwconv_ln_groups",
-    "gp_dwconv7_raw_stats": H + "test_dwconv7_raw_stats_and_lnfold_gemm",
-    "gp_layernorm": H + "test_layernorm",
-    "gp_groupnorm_chunks": H + "test_groupnorm",
-    "gp_groupnorm_stats": H + "test_groupnorm",
-    "gp_groupnorm_apply": H + "test_groupnorm",
-    "gp_groupnorm_upsample2x": H + "test_groupnorm_upsample2x_bitwise_vs_two_passes",
+    "gp_dwconv7_raw_stats": NC + "test_dwconv7_raw_stats",
+    "gp_layernorm": NC + "test_layernorm",
+    "gp_groupnorm_chunks": NC + "test_groupnorm",
+    "gp_groupnorm_stats": NC + "test_groupnorm",
+    "gp_groupnorm_apply": NC + "test_groupnorm",
+    "gp_groupnorm_upsample2x": NC + "test_groupnorm_upsample2x",
     "gp_groupnorm_apply_xyz": H + "test_groupnorm_apply_xyz",
-    "gp_upsample_bilinear2x": H + "test_upsample_and_col2im",
+    "gp_upsample_bilinear2x": NC + "test_upsample_bilinear2x",
     "gp_deconv_col2im": H + "test_upsample_and_col2im",
     "gp_xyz_out_layer": H + "test_xyz_out_pointwise_smallcin",
     "gp_pointwise_k3": H + "test_xyz_out_pointwise_smallcin",
