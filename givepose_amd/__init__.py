@@ -8,6 +8,8 @@ Public surface mirrors the reference for this path:
   PoseNetConfig      the absl FLAGS the path reads (config/config.py)
   compute_degree_cm_mAP, MapAccumulator, paper_table
                      evaluation/eval_utils_cass.py:490-820 and the tables evaluate.py:160-280 logs, on the device (evalmap.py)
+  pose_from_umeyama, pose_from_umeyama_device
+                     tools/umeyama.py:17-60 (RANSAC Umeyama alignment of the NOCS map to the depth), on the device (umeyama.py)
 """
 from .config import PoseNetConfig  # noqa: F401
 from .posenet import PoseNet  # noqa: F401
@@ -34,4 +36,7 @@ def __getattr__(name):
     if name in ("compute_degree_cm_mAP", "MapAccumulator", "paper_table"):      # evaluation/eval_utils_cass.py:490
         from . import evalmap
         return getattr(evalmap, name)
+    if name in ("pose_from_umeyama", "pose_from_umeyama_device"):                # tools/umeyama.py:17
+        from . import umeyama
+        return getattr(umeyama, name)
     raise AttributeError(name)

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # GP_LIB_PATH: A/B runs of two builds on one box (scripts/race_probe.py); the default is the in-tree library
 LIB_PATH = os.environ.get("GP_LIB_PATH") or os.path.join(_HERE, "libgivepose_hip.so")
 
-ABI_VERSION = 327       # include/givepose_hip.h GP_ABI_VERSION: gp_gemm_desc layout (checked against gp_version() at load)
+ABI_VERSION = 328       # include/givepose_hip.h GP_ABI_VERSION: gp_gemm_desc layout (checked against gp_version() at load)
 GP_F32, GP_F16, GP_F64 = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_LRELU = 0, 1, 2, 3
 EPI_NONE, EPI_GELU, EPI_RELU, EPI_LRELU, EPI_SCALE_RES, EPI_RES_RELU, EPI_LNFOLD_GELU = 0, 1, 2, 3, 4, 5, 6
@@ -102,6 +102,16 @@ PROTOTYPES = {
     "gp_timing_top": ([c_int, c_char_p, c_int, POINTER(c_int), POINTER(c_long), POINTER(c_double), POINTER(c_double), POINTER(c_double)], c_int),
 }
 
+# the alignment family (include/givepose_align.h, prefix gpa_; tests/test_umeyama_cpu.py checks both ways)
+ALIGN_PROTOTYPES = {
+    "gpa_backproject": ([_P] * 5 + [c_int] * 3 + [_P] * 5, c_int),
+    "gpa_umeyama": ([_P] * 3 + [c_int] + [_P] * 8, c_int),
+    "gpa_crop_depth": ([_P] * 5 + [c_int] * 5 + [_P], c_int),
+}
+GPA_RES, GPA_MAX_POINTS, GPA_MAX_ITER, GPA_SAMPLE = 64, 4096, 128, 5
+GPA_HYP_STRIDE, GPA_FIT_STRIDE, GPA_FIT32_STRIDE, GPA_RECORD = 16, 16, 13, 5
+GPA_OK, GPA_NO_POINTS, GPA_LOW_INLIERS, GPA_DEGENERATE = 0, 1, 2, 3      # enum gpa_status
+
 _lib = None
 
 
@@ -119,7 +129,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -m givepose_amd.build` (hipcc --offload-arch=gfx950). "
             "There is no CPU or PyTorch fallback for the product path.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (argtypes, restype) in PROTOTYPES.items():
+    for name, (argtypes, restype) in list(PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.argtypes = argtypes
         fn.restype = restype

@@ -300,6 +300,15 @@ __device__ __forceinline__ float group_max(float v, int width) {
     return v;
 }
 
+// Source pixel of destination pixel (x, y) under the inverted 2x3 affine map m: cv::warpAffine's fixed-point walk (AB_BITS = 10,
+// round-half-even of the double products).  Shared by gp_crop_rois (misc.hip) and gpa_crop_depth (align.hip), which must agree.
+__device__ __forceinline__ bool warp_src(const double* __restrict__ m, int x, int y, int W, int H, int& X, int& Y) {
+    const int X0 = __double2int_rn((m[1] * y + m[2]) * 1024.0) + 512, Y0 = __double2int_rn((m[4] * y + m[5]) * 1024.0) + 512;
+    X = (X0 + __double2int_rn(m[0] * x * 1024.0)) >> 10;
+    Y = (Y0 + __double2int_rn(m[3] * x * 1024.0)) >> 10;
+    return (unsigned)X < (unsigned)W && (unsigned)Y < (unsigned)H;
+}
+
 // 256 zero bytes per translation unit: source of LDS-DMA lanes that fall in padding / out of range
 static __device__ __attribute__((aligned(256), used)) unsigned int gp_zero_page_tu[64];
 

@@ -209,12 +209,7 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(const float* __restrict_
 // ------------------------------------------------------------------------------------- crop pre-processing
 // One thread per destination pixel of the S x S crop (image + mask) or of the R x R crop (coordinate grid); the
 // fixed-point source coordinate is cv::warpAffine's (AB_BITS = 10, round-half-even of the double products).
-__device__ __forceinline__ bool warp_src(const double* __restrict__ m, int x, int y, int W, int H, int& X, int& Y) {
-    const int X0 = __double2int_rn((m[1] * y + m[2]) * 1024.0) + 512, Y0 = __double2int_rn((m[4] * y + m[5]) * 1024.0) + 512;
-    X = (X0 + __double2int_rn(m[0] * x * 1024.0)) >> 10;
-    Y = (Y0 + __double2int_rn(m[3] * x * 1024.0)) >> 10;
-    return (unsigned)X < (unsigned)W && (unsigned)Y < (unsigned)H;
-}
+// (warp_src, the source pixel of a destination pixel, lives in common.hpp: gpa_crop_depth of align.hip walks the same map)
 
 __global__ __launch_bounds__(256) void crop_rois_kernel(const unsigned char* __restrict__ frames,
                                                         const unsigned char* __restrict__ masks,

@@ -185,3 +185,38 @@ class RoiCropper:
         for k in ("roi_wh", "bbox_center", "resize_ratio"):
             buf(k, P[k].shape).copy_(torch.from_numpy(P[k]).pin_memory(), non_blocking=True)
         return out
+
+    def crop_depth(self, depth_frames, frame_idx, bboxes, out=None):
+        """depth_frames (F,H,W) fp32 on the device (or host: copied), in the caller's unit; frame_idx / bboxes as in __call__.
+        Writes roi_depth (B,1,R,R) and roi_pix_2d (B,2,R,R) -- per output pixel of the out_res crop the NEAREST source pixel's depth
+        and its pixel x / y, 0 outside the frame -- into `out` or fresh tensors (gpa_crop_depth, include/givepose_align.h): the
+        depth and the pixel coordinates on the grid of roi_coord_2d, which the alignment of umeyama.py needs."""
+        dev = self.device
+        depth = torch.as_tensor(depth_frames).to(dev, torch.float32).contiguous()
+        if depth.dim() != 3 or tuple(depth.shape[1:]) != (self.H, self.W):
+            raise ValueError(f"depth frames {tuple(depth.shape)} do not match (F,{self.H},{self.W})")
+        F = depth.shape[0]
+        fi = np.asarray(frame_idx, dtype=np.int32).reshape(-1)
+        B = len(fi)
+        if len(bboxes) != B:
+            raise ValueError("frame_idx and bboxes must have one entry per detection")
+        if B == 0 or fi.min() < 0 or fi.max() >= F:
+            raise ValueError("frame_idx out of range")      # the kernel trusts it
+        P = crop_params(bboxes, self.H, self.W, self.S, self.R, self.pad)
+        if out is None:
+            out = {}
+        bufs = []
+        for name, shape in (("roi_depth", (B, 1, self.R, self.R)), ("roi_pix_2d", (B, 2, self.R, self.R))):
+            t = out.get(name)
+            if t is None:
+                t = out[name] = torch.empty(shape, device=dev, dtype=torch.float32)
+            if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"out[{name!r}] must be a contiguous fp32 {shape} tensor on {dev}")
+            bufs.append(t)
+        inv = torch.from_numpy(P["inv_out"].reshape(-1)).pin_memory().to(dev, non_blocking=True)
+        idx = torch.from_numpy(fi).pin_memory().to(dev, non_blocking=True)
+        L = _lib.load()
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(L.gpa_crop_depth(depth.data_ptr(), idx.data_ptr(), inv.data_ptr(), bufs[0].data_ptr(), bufs[1].data_ptr(),
+                                    B, F, self.H, self.W, self.R, stream), "gpa_crop_depth")
+        return out

@@ -50,7 +50,7 @@ enum gp_epilogue {
 };
 
 const char* gp_last_error(void);
-#define GP_ABI_VERSION 327 /* 327: + gp_dcnv3_xyz_project (encoder layer 0 as one gather + one projection); 326: + gp_eval_normalise, gp_eval_pair_overlaps, gp_eval_match, gp_eval_ap (degree-cm / 3D-IoU mAP on the device); 325: + gp_attention64_hd, gp_patchify_pnp, gp_layernorm at non-power-of-two vector counts (C = 192); 324: + gp_pnp_conv1_masked, gp_pool_mmm, gp_pose_tail_rt; round 6: + gp_dwconv_ln_groups (322), gp_convnext_mlp_pack_w2_s32 / GP_MLP_S32 (323); 321 = round 5: gp_gemm_desc.gn_rows + gp_gemm_gn_rows (321); gp_gemm variants 19-22, gp_convnext_mlp C = 512 (no layout change); 311 = round 4 (+ gp_groupnorm_upsample2x); 310 = round 3 (gp_gemm_desc: split-operand / fp32 residual stream fields); 200 = round 2 */
+#define GP_ABI_VERSION 328 /* 328: + the alignment family gpa_backproject, gpa_umeyama, gpa_crop_depth, declared in givepose_align.h (RANSAC Umeyama pose from the NOCS map and depth); 327: + gp_dcnv3_xyz_project (encoder layer 0 as one gather + one projection); 326: + gp_eval_normalise, gp_eval_pair_overlaps, gp_eval_match, gp_eval_ap (degree-cm / 3D-IoU mAP on the device); 325: + gp_attention64_hd, gp_patchify_pnp, gp_layernorm at non-power-of-two vector counts (C = 192); 324: + gp_pnp_conv1_masked, gp_pool_mmm, gp_pose_tail_rt; round 6: + gp_dwconv_ln_groups (322), gp_convnext_mlp_pack_w2_s32 / GP_MLP_S32 (323); 321 = round 5: gp_gemm_desc.gn_rows + gp_gemm_gn_rows (321); gp_gemm variants 19-22, gp_convnext_mlp C = 512 (no layout change); 311 = round 4 (+ gp_groupnorm_upsample2x); 310 = round 3 (gp_gemm_desc: split-operand / fp32 residual stream fields); 200 = round 2 */
 int gp_version(void);   /* == GP_ABI_VERSION of the header the library was built from */
 /* device properties the host needs: CU count and arch string ("gfx950...") */
 int gp_device_info(int* cu_count, char* arch, int arch_len);
