@@ -10,6 +10,9 @@ Public surface mirrors the reference for this path:
                      evaluation/eval_utils_cass.py:490-820 and the tables evaluate.py:160-280 logs, on the device (evalmap.py)
   pose_from_umeyama, pose_from_umeyama_device
                      tools/umeyama.py:17-60 (RANSAC Umeyama alignment of the NOCS map to the depth), on the device (umeyama.py)
+  PoseLoss, LossConfig, LossAccumulator
+                     losses/pose_loss.py:13-196 (the six validation-loss terms of a batch, forward values only), on the device
+                     (loss.py); PoseNet.forward(..., do_loss=True) returns the predictions it reads
 """
 from .config import PoseNetConfig  # noqa: F401
 from .posenet import PoseNet  # noqa: F401
@@ -39,4 +42,7 @@ def __getattr__(name):
     if name in ("pose_from_umeyama", "pose_from_umeyama_device"):                # tools/umeyama.py:17
         from . import umeyama
         return getattr(umeyama, name)
+    if name in ("PoseLoss", "LossConfig", "LossAccumulator"):                    # losses/pose_loss.py:13
+        from . import loss
+        return getattr(loss, name)
     raise AttributeError(name)

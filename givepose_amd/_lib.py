@@ -112,6 +112,14 @@ GPA_RES, GPA_MAX_POINTS, GPA_MAX_ITER, GPA_SAMPLE = 64, 4096, 128, 5
 GPA_HYP_STRIDE, GPA_FIT_STRIDE, GPA_FIT32_STRIDE, GPA_RECORD = 16, 16, 13, 5
 GPA_OK, GPA_NO_POINTS, GPA_LOW_INLIERS, GPA_DEGENERATE = 0, 1, 2, 3      # enum gpa_status
 
+# the validation-loss family (include/givepose_loss.h, prefix gpl_; tests/test_pose_loss_cpu.py checks both ways)
+LOSS_PROTOTYPES = {
+    "gpl_pose_decode_train": ([_P] * 6 + [c_int, c_int, c_double, c_int] + [_P] * 5, c_int),
+    "gpl_pose_loss_partials": ([_P] * 16 + [c_int] * 6 + [_P] * 3, c_int),
+    "gpl_pose_loss_reduce": ([_P, _P, c_int, c_int, c_int] + [c_double] * 5 + [_P] * 4, c_int),
+}
+GPL_RES, GPL_SYM, GPL_SPLIT, GPL_PART, GPL_RECORD, GPL_OUT, GPL_ACC = 64, 360, 4, 8, 8, 8, 10
+
 _lib = None
 
 
@@ -129,7 +137,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -m givepose_amd.build` (hipcc --offload-arch=gfx950). "
             "There is no CPU or PyTorch fallback for the product path.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (argtypes, restype) in list(PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()):
+    for name, (argtypes, restype) in list(PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.argtypes = argtypes
         fn.restype = restype

@@ -911,9 +911,20 @@ class PoseNet(nn.Module):
 
     @torch.no_grad()
     def forward(self, data, device="cuda", do_loss=False, pred_scale=None, groups=None):
-        """Reference signature (network/PoseNet.py:173).  ``do_loss`` (training) is out of scope.  groups (extension): see forward_device."""
+        """Reference signature (network/PoseNet.py:173).  groups (extension): see forward_device.
+
+        do_loss=True is the reference's validation / train-time forward, values only (no gradient): the network reads
+        ``data['roi_mask_deform']`` in the place of ``roi_mask`` and the pose is decoded by pose_from_predictions_train
+        (gpl_pose_decode_train, a plain launch after the forward's graph), which keeps ``rot`` on the device.  The result feeds
+        givepose_amd.PoseLoss."""
         if do_loss:
-            raise NotImplementedError("training path (do_loss=True) is out of scope for the inference build")
+            from . import loss
+            cfg = self.cfg
+            out = self.forward_device({**data, "roi_mask": data["roi_mask_deform"]}, device, groups=groups)
+            rot, trans = loss.pose_decode_train(out["pred_t"], out["rot_allo"], data["cam_K"], data["bbox_center"], data["resize_ratio"],
+                                                data["roi_wh"], t_site=cfg.t_type == "site", is_allo=ROT_TYPES[cfg.r_type][2], eps=1e-4)
+            return {"rot": rot, "trans": trans, "size": out["size"].clone(), "mask": out["mask"].clone(),
+                    "nocs_coor": out["nocs_coor"].clone(), "ivfc_coor": out["ivfc_coor"].clone()}
         out = self.forward_device(data, device, groups=groups)
         # the reference returns rot as a CPU tensor (pose_from_pred_centroid_z.py:157) and fresh tensors
         return {"rot": out["rot"].cpu(), "trans": out["trans"].clone(), "size": out["size"].clone(),
