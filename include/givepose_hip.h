@@ -67,6 +67,11 @@ int gp_device_info(int* cu_count, char* arch, int arch_len);
  *   mask_is_logits != 0: `mask` holds pre-softmax logits and the kernel applies the softmax over
  *     the P taps of each group (fuses modules/dcnv3.py:331-333 into the gather).
  *   Requires batch <= im2col_step or batch % im2col_step == 0 like dcnv3_cuda.cu:46-49.
+ *   Inputs must be FINITE.  The wave kernels fetch an out-of-range tap from pixel (0,0) and a corner
+ *     outside the map from the clamped pixel, and multiply by a zero weight where the reference CUDA
+ *     skips the load: a NaN / Inf input pixel can therefore reach outputs that the reference keeps
+ *     finite.  Callers that need the reference's behaviour on non-finite inputs use
+ *     gp_dcnv3_forward_any, which selects such values away (tests/test_dcnv3_conformance_gpu.py).
  */
 int gp_dcnv3_forward(const void* in, const void* offset, const void* mask, void* out, int N, int H, int W,
                      int G, int D, int K, int stride, int pad, int dil, float offset_scale,

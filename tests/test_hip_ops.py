@@ -3,6 +3,8 @@ CPU reference of the same op (DCNv3: the oracle restatement of the reference CUD
 
 Tolerances: fp32 storage path 2e-5 relative-to-scale (fp32 MFMA/accumulate, summation order differs);
 fp16 storage path 4e-3 relative-to-scale (fp16 rounding of inputs/outputs, fp32 accumulate).
+The DCNv3 forward per element against a float64 reference with a derived bound, on non-square maps and on the sampling edges:
+tests/test_dcnv3_conformance_gpu.py.
 """
 import ctypes
 import os

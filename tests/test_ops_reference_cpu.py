@@ -142,13 +142,14 @@ E = "tests/test_evalmap_gpu.py::test_kernels_against_reference_fixtures"
 P = "tests/test_pnp_flags_gpu.py::"
 NC = "tests/test_norm_conformance_gpu.py::"
 A = "tests/test_att_pnp_gpu.py::"
+DC = "tests/test_dcnv3_conformance_gpu.py::"
 # entry point -> the operator-level test that holds it against a reference of its own operation (never a whole-network test); graph,
 # timing, version and device-info calls -> the test that exercises them
 CLOSURE = {
     "gp_version": "tests/test_abi.py::test_ctypes_prototypes_cover_header",
     "gp_device_info": M + "test_device_info",
-    "gp_dcnv3_forward": H + "test_dcnv3_fused_softmax_and_strided_om",
-    "gp_dcnv3_forward_any": H + "test_dcnv3_vs_oracle",
+    "gp_dcnv3_forward": DC + "test_dcnv3_forward",
+    "gp_dcnv3_forward_any": DC + "test_dcnv3_forward",
     "gp_dcnv3_backward": "tests/test_hip_dcnv3_any.py::test_backward_stride2_quarter_buffer_and_autograd_function",
     "gp_gemm": "tests/test_gemm_conformance.py::test_gemm_conformance",
     "gp_gemm_gn_rows": H + "test_gemm_small_m_latency_variant",
