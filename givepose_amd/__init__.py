@@ -13,6 +13,9 @@ Public surface mirrors the reference for this path:
   PoseLoss, LossConfig, LossAccumulator
                      losses/pose_loss.py:13-196 (the six validation-loss terms of a batch, forward values only), on the device
                      (loss.py); PoseNet.forward(..., do_loss=True) returns the predictions it reads
+  PoseLoss.value_and_grad, PoseLoss.with_grad, pose_decode_train, pose_decode_train_backward, PoseNet.head_grads
+                     the gradient of the total loss at the network's raw outputs (the loss half of `total_loss.backward()`,
+                     engine/train.py:115-121), on the device (loss.py)
 """
 from .config import PoseNetConfig  # noqa: F401
 from .posenet import PoseNet  # noqa: F401
@@ -42,7 +45,7 @@ def __getattr__(name):
     if name in ("pose_from_umeyama", "pose_from_umeyama_device"):                # tools/umeyama.py:17
         from . import umeyama
         return getattr(umeyama, name)
-    if name in ("PoseLoss", "LossConfig", "LossAccumulator"):                    # losses/pose_loss.py:13
+    if name in ("PoseLoss", "LossConfig", "LossAccumulator", "pose_decode_train", "pose_decode_train_backward"):   # losses/pose_loss.py:13
         from . import loss
         return getattr(loss, name)
     raise AttributeError(name)

@@ -120,6 +120,13 @@ LOSS_PROTOTYPES = {
 }
 GPL_RES, GPL_SYM, GPL_SPLIT, GPL_PART, GPL_RECORD, GPL_OUT, GPL_ACC = 64, 360, 4, 8, 8, 8, 10
 
+# the loss-gradient family (include/givepose_grad.h, prefix gpg_; tests/test_pose_loss_grad_cpu.py checks both ways)
+GRAD_PROTOTYPES = {
+    "gpg_pose_loss_grad": ([_P] * 19 + [c_int] * 6 + [c_double] * 5 + [_P] * 7, c_int),
+    "gpg_pose_decode_train_backward": ([_P] * 9 + [c_int, c_int, c_double, c_int] + [_P] * 5, c_int),
+}
+GPG_TERMS, GPG_SMALL, GPG_DECODE = 6, 15, 18
+
 _lib = None
 
 
@@ -137,7 +144,8 @@ def load():
             f"{LIB_PATH} not found: build it with `python -m givepose_amd.build` (hipcc --offload-arch=gfx950). "
             "There is no CPU or PyTorch fallback for the product path.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (argtypes, restype) in list(PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items()):
+    for name, (argtypes, restype) in (list(PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items())
+                                      + list(GRAD_PROTOTYPES.items())):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.argtypes = argtypes
         fn.restype = restype

@@ -12,6 +12,9 @@ results are the float64 ones rounded once.  Two calls on the same inputs give th
 One documented difference: with a 'sym' r_type the reference zeroes the x and z coordinates of the symmetric crops' points in the
 CALLER's `data['model_point']` (through a permuted view, pose_loss.py:163-168).  Here `model_point` is only read.
 
+The gradients of these values live in their own family (include/givepose_grad.h, gpg_*): `PoseLoss.value_and_grad`,
+`PoseLoss.with_grad` (the autograd binding a training loop calls) and `pose_decode_train_backward` below.
+
 HIP devices only; there is no CPU fallback.
 """
 import dataclasses
@@ -24,6 +27,7 @@ from .config import ROT_TYPES
 
 KEYS = ("Rot1", "Tran", "Size", "Point_matching", "nocs_coor", "sp2d_coor")
 RECORD_COLUMNS = ("index", "re_best", "re", "te", "rot1_sum", "tran_sum", "size_sum", "branch")
+GRAD_KEYS = ("rot", "trans", "size", "nocs_coor", "ivfc_coor")
 
 
 @dataclasses.dataclass(frozen=True)
@@ -104,6 +108,60 @@ def pose_decode_train(pred_t, rot_allo, cam_K, bbox_center, resize_ratio, roi_wh
     return rot32, trans32
 
 
+def pose_decode_train_backward(g_rot_ego, g_trans, pred_t, rot_allo, cam_K, bbox_center, resize_ratio, roi_wh, rot6d=None, t_site=True,
+                               is_allo=True, eps=1e-4, return_details=False):
+    """Backward of `pose_decode_train` (gpg_pose_decode_train_backward): the upstream gradients of its two results, then its own
+    inputs -> {"rot_allo": (B,3,3), "pred_t": (B,3)} float32 on the device of `rot_allo`.  rot6d (B,6): the raw vector `rot_allo`
+    was decoded from by rot6d_to_mat_batch; the dict then also holds its gradient, "rot6d" (B,6).
+    return_details: a second value, the (B,18) float64 record (d rot_allo, d pred_t, d rot6d)."""
+    rot_allo = torch.as_tensor(rot_allo)
+    dev = rot_allo.device
+    if dev.type != "cuda":
+        raise _lib.GivePoseHipError("pose_decode_train_backward runs on a HIP device only: there is no CPU path")
+    B = rot_allo.shape[0]
+    if B == 0:
+        raise ValueError("empty batch")
+    ge, gt = _f32(g_rot_ego, dev, (B, 3, 3), "g_rot_ego"), _f32(g_trans, dev, (B, 3), "g_trans")
+    pt, Ra, K = _f32(pred_t, dev, (B, 3), "pred_t"), _f32(rot_allo, dev, (B, 3, 3), "rot_allo"), _f32(cam_K, dev, (B, 3, 3), "cam_K")
+    ce, wh = _f32(bbox_center, dev, (B, 2), "bbox_center"), _f32(roi_wh, dev, (B, 2), "roi_wh")
+    ra = _f32(torch.as_tensor(resize_ratio).reshape(-1), dev, (B,), "resize_ratio")
+    r6 = None if rot6d is None else _f32(rot6d, dev, (B, 6), "rot6d")
+    out = {"rot_allo": torch.empty(B, 3, 3, device=dev), "pred_t": torch.empty(B, 3, device=dev)}
+    if r6 is not None:
+        out["rot6d"] = torch.empty(B, 6, device=dev)
+    g64 = torch.empty(B, _lib.GPG_DECODE, device=dev, dtype=torch.float64)
+    L = _lib.load()
+    with torch.cuda.device(dev):
+        _lib.check(L.gpg_pose_decode_train_backward(ge.data_ptr(), gt.data_ptr(), pt.data_ptr(), Ra.data_ptr(), K.data_ptr(), ce.data_ptr(),
+                                                    ra.data_ptr(), wh.data_ptr(), r6.data_ptr() if r6 is not None else 0,
+                                                    int(bool(t_site)), int(bool(is_allo)), float(eps), B, out["rot_allo"].data_ptr(),
+                                                    out["pred_t"].data_ptr(), out["rot6d"].data_ptr() if r6 is not None else 0,
+                                                    g64.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
+                   "gpg_pose_decode_train_backward")
+    return (out, g64) if return_details else out
+
+
+class _PoseLossFunction(torch.autograd.Function):
+    """The six terms as one node of the autograd graph: five differentiable inputs, six outputs."""
+
+    @staticmethod
+    def forward(ctx, loss, data, *pred):
+        a, dims = loss._inputs(dict(zip(GRAD_KEYS, pred)), data)
+        out64, out32, record, slabs = loss._forward(a, dims)
+        ctx.loss, ctx.dims, ctx.like = loss, dims, [(p.dtype, p.device) for p in pred]
+        ctx.save_for_backward(*a, slabs, record)
+        return tuple(out32[i].clone() for i in range(len(KEYS)))
+
+    @staticmethod
+    def backward(ctx, *gouts):
+        *a, slabs, record = ctx.saved_tensors
+        dev = record.device
+        gout = torch.stack([torch.zeros((), device=dev, dtype=torch.float64) if g is None else g.to(dev, torch.float64).reshape(())
+                            for g in gouts])
+        grads, _ = ctx.loss._backward(a, ctx.dims, slabs, record, gout)
+        return (None, None) + tuple(grads[k].to(device=d, dtype=t) for k, (t, d) in zip(GRAD_KEYS, ctx.like))
+
+
 class PoseLoss:
     """`PoseLoss()(pred_dict, data)` of the reference: a dict of 0-dim float32 device tensors with the keys Rot1, Tran, Size,
     Point_matching, nocs_coor, sp2d_coor, in that order.  pred_dict: rot (B,3,3), trans, size (B,3), nocs_coor, ivfc_coor
@@ -120,8 +178,8 @@ class PoseLoss:
             raise ValueError("PoseLoss needs a LossConfig")
         self.cfg = cfg
 
-    def _launch(self, pred_dict, data, acc=None):
-        cfg = self.cfg
+    def _inputs(self, pred_dict, data):
+        """-> (the sixteen float32 / int32 device tensors of gpl_pose_loss_partials, (B, P, device))."""
         rot = torch.as_tensor(pred_dict["rot"])
         dev = rot.device
         if dev.type != "cuda":
@@ -145,6 +203,11 @@ class PoseLoss:
              f(data["roi_mask_output"], (B, 1, R, R), "roi_mask_output"), f(data["roi_ivfc_mask_output"], (B, 1, R, R), "roi_ivfc_mask_output"),
              f(data["nocs_coord"], (B, 3, R, R), "nocs_coord"), f(data["ivfc_coord"], (B, 3, R, R), "ivfc_coord"),
              f(mp, (B, P, 3), "model_point"), _sym_table(dev)]
+        return a, (B, P, dev)
+
+    def _forward(self, a, dims, acc=None):
+        cfg, R = self.cfg, _lib.GPL_RES
+        B, P, dev = dims
         slabs = torch.empty(B, _lib.GPL_SPLIT, _lib.GPL_PART, device=dev, dtype=torch.float64)
         record = torch.empty(B, _lib.GPL_RECORD, device=dev, dtype=torch.float64)
         out64 = torch.empty(_lib.GPL_OUT, device=dev, dtype=torch.float64)
@@ -159,7 +222,62 @@ class PoseLoss:
             _lib.check(L.gpl_pose_loss_reduce(slabs.data_ptr(), record.data_ptr(), B, P, angle, float(cfg.rot_1_w), float(cfg.tran_w),
                                               float(cfg.size_w), float(cfg.prop_pm_w), float(cfg.coor_w), out64.data_ptr(), out32.data_ptr(),
                                               acc.data_ptr() if acc is not None else 0, stream), "gpl_pose_loss_reduce")
-        return out64, out32, record
+        return out64, out32, record, slabs
+
+    def _backward(self, a, dims, slabs, record, gout):
+        """One launch of gpg_pose_loss_grad -> (the five float32 gradients by GRAD_KEYS, the (B,15) float64 record of the small ones)."""
+        cfg, R = self.cfg, _lib.GPL_RES
+        B, P, dev = dims
+        if gout is not None:
+            gout = torch.as_tensor(gout)
+            if tuple(gout.shape) != (_lib.GPG_TERMS,):
+                raise ValueError(f"gout must be ({_lib.GPG_TERMS},), not {tuple(gout.shape)}")
+            gout = gout.detach().to(dev, torch.float64).contiguous()
+        g = {"rot": torch.empty(B, 3, 3, device=dev), "trans": torch.empty(B, 3, device=dev), "size": torch.empty(B, 3, device=dev),
+             "nocs_coor": torch.empty(B, 3, R, R, device=dev), "ivfc_coor": torch.empty(B, 3, R, R, device=dev)}
+        small = torch.empty(B, _lib.GPG_SMALL, device=dev, dtype=torch.float64)
+        L = _lib.load()
+        with torch.cuda.device(dev):
+            _lib.check(L.gpg_pose_loss_grad(*[t.data_ptr() for t in a], slabs.data_ptr(), record.data_ptr(),
+                                            gout.data_ptr() if gout is not None else 0, B, P, R, int("sym" in cfg.r_type),
+                                            int(cfg.r_loss == "angle"), int(cfg.pose_loss_type == "smoothl1"), float(cfg.rot_1_w),
+                                            float(cfg.tran_w), float(cfg.size_w), float(cfg.prop_pm_w), float(cfg.coor_w),
+                                            *[g[k].data_ptr() for k in GRAD_KEYS], small.data_ptr(),
+                                            torch.cuda.current_stream(dev).cuda_stream), "gpg_pose_loss_grad")
+        return g, small
+
+    def _launch(self, pred_dict, data, acc=None):
+        a, dims = self._inputs(pred_dict, data)
+        return self._forward(a, dims, acc)[:3]
+
+    def _details(self, out64, out32, record):
+        details = {"terms": out64[:6], "mean_re": out64[6], "mean_te": out64[7], "out32": out32, "record": record}
+        details.update({k: record[:, i] for i, k in enumerate(RECORD_COLUMNS)})
+        return details
+
+    @torch.no_grad()
+    def value_and_grad(self, pred_dict, data, gout=None, return_details=False):
+        """-> (the loss dict of `__call__`, {rot, trans, size, nocs_coor, ivfc_coor}: the float32 gradients of
+        sum_k gout[k] * term_k with respect to the five predictions).  gout: six weights in KEYS order (a device tensor stays on
+        the device), None = ones: the gradient of the total loss.  Two forward launches and one gradient launch, no host sync.
+        The closest ground truth and the rotated ground-truth maps are constants, as in the reference.
+        return_details: a third value, the details of `__call__` plus `small64`, the (B,15) float64 d rot / d trans / d size."""
+        a, dims = self._inputs(pred_dict, data)
+        out64, out32, record, slabs = self._forward(a, dims)
+        grads, small = self._backward(a, dims, slabs, record, gout)
+        loss = {k: out32[i] for i, k in enumerate(KEYS)}
+        if not return_details:
+            return loss, grads
+        return loss, grads, {**self._details(out64, out32, record), "small64": small}
+
+    def with_grad(self, pred_dict, data):
+        """The loss dict of `__call__`, attached to the autograd graph: `sum(d.values()).backward()` (or any other function of
+        the six terms) fills `.grad` of the five prediction tensors through gpg_pose_loss_grad, as the reference's
+        `total_loss.backward()` does.  The predictions must be device tensors."""
+        pred = [pred_dict[k] for k in GRAD_KEYS]
+        if not all(torch.is_tensor(p) and p.device.type == "cuda" for p in pred):
+            raise _lib.GivePoseHipError("PoseLoss runs on a HIP device only: there is no CPU path")
+        return dict(zip(KEYS, _PoseLossFunction.apply(self, data, *pred)))
 
     @torch.no_grad()
     def __call__(self, pred_dict, data, return_details=False):
@@ -167,9 +285,7 @@ class PoseLoss:
         loss = {k: out32[i] for i, k in enumerate(KEYS)}
         if not return_details:
             return loss
-        details = {"terms": out64[:6], "mean_re": out64[6], "mean_te": out64[7], "out32": out32, "record": record}
-        details.update({k: record[:, i] for i, k in enumerate(RECORD_COLUMNS)})
-        return loss, details
+        return loss, self._details(out64, out32, record)
 
 
 class LossAccumulator:

@@ -918,14 +918,42 @@ class PoseNet(nn.Module):
         (gpl_pose_decode_train, a plain launch after the forward's graph), which keeps ``rot`` on the device.  The result feeds
         givepose_amd.PoseLoss."""
         if do_loss:
-            from . import loss
-            cfg = self.cfg
-            out = self.forward_device({**data, "roi_mask": data["roi_mask_deform"]}, device, groups=groups)
-            rot, trans = loss.pose_decode_train(out["pred_t"], out["rot_allo"], data["cam_K"], data["bbox_center"], data["resize_ratio"],
-                                                data["roi_wh"], t_site=cfg.t_type == "site", is_allo=ROT_TYPES[cfg.r_type][2], eps=1e-4)
-            return {"rot": rot, "trans": trans, "size": out["size"].clone(), "mask": out["mask"].clone(),
-                    "nocs_coor": out["nocs_coor"].clone(), "ivfc_coor": out["ivfc_coor"].clone()}
+            return self._forward_do_loss(data, device, groups)[0]
         out = self.forward_device(data, device, groups=groups)
         # the reference returns rot as a CPU tensor (pose_from_pred_centroid_z.py:157) and fresh tensors
         return {"rot": out["rot"].cpu(), "trans": out["trans"].clone(), "size": out["size"].clone(),
                 "mask": out["mask"].clone(), "nocs_coor": out["nocs_coor"].clone(), "ivfc_coor": out["ivfc_coor"].clone()}
+
+    def _forward_do_loss(self, data, device, groups):
+        """-> (the dict of forward(do_loss=True), the raw head outputs the pose was decoded from: pred_rot, pred_t, rot_allo)."""
+        from . import loss
+        cfg = self.cfg
+        out = self.forward_device({**data, "roi_mask": data["roi_mask_deform"]}, device, groups=groups)
+        raw = {k: out[k].clone() for k in ("pred_rot", "pred_t", "rot_allo")}
+        rot, trans = loss.pose_decode_train(raw["pred_t"], raw["rot_allo"], data["cam_K"], data["bbox_center"], data["resize_ratio"],
+                                            data["roi_wh"], t_site=cfg.t_type == "site", is_allo=ROT_TYPES[cfg.r_type][2], eps=1e-4)
+        return {"rot": rot, "trans": trans, "size": out["size"].clone(), "mask": out["mask"].clone(),
+                "nocs_coor": out["nocs_coor"].clone(), "ivfc_coor": out["ivfc_coor"].clone()}, raw
+
+    @torch.no_grad()
+    def head_grads(self, data, pose_loss, device="cuda", gout=None, groups=None):
+        """The loss half of a training step: forward(do_loss=True), `pose_loss` (a givepose_amd.PoseLoss; `data` also holds the
+        ground truth it reads), the loss gradient and the backward of the train-time pose decode, everything on the device.
+        -> {"loss": the six terms, "output": the dict of forward(do_loss=True), "grads": {"rot6d", "pred_t", "size", "nocs_coor",
+        "ivfc_coor"}}: the gradient of sum_k gout[k] * term_k (gout None: the total loss) at the tensors the heads emit -- the
+        ConvPnPNet rotation vector, pred_t, the size head's output (pred_size = head + norm_mean_size, so d head = d size) and
+        the two coordinate maps.  The backward pass through the network is not part of this library.
+
+        For an r_type whose raw vector is not decoded by rot6d_to_mat_batch (kind != 0 in config.ROT_TYPES: the fixed-axis 6d
+        forms, quaternion, Euler) grads["rot6d"] is the gradient of the (B,3,3) allocentric rotation matrix `rot_allo` instead."""
+        from . import loss
+        cfg = self.cfg
+        out, raw = self._forward_do_loss(data, device, groups)
+        terms, g = pose_loss.value_and_grad(out, data, gout=gout)
+        kind, is_allo = ROT_TYPES[cfg.r_type][1], ROT_TYPES[cfg.r_type][2]
+        d = loss.pose_decode_train_backward(g["rot"], g["trans"], raw["pred_t"], raw["rot_allo"], data["cam_K"], data["bbox_center"],
+                                            data["resize_ratio"], data["roi_wh"], rot6d=raw["pred_rot"] if kind == 0 else None,
+                                            t_site=cfg.t_type == "site", is_allo=is_allo, eps=1e-4)
+        return {"loss": terms, "output": out,
+                "grads": {"rot6d": d["rot6d"] if kind == 0 else d["rot_allo"], "pred_t": d["pred_t"], "size": g["size"],
+                          "nocs_coor": g["nocs_coor"], "ivfc_coor": g["ivfc_coor"]}}
