@@ -16,6 +16,10 @@ Public surface mirrors the reference for this path:
   PoseLoss.value_and_grad, PoseLoss.with_grad, pose_decode_train, pose_decode_train_backward, PoseNet.head_grads
                      the gradient of the total loss at the network's raw outputs (the loss half of `total_loss.backward()`,
                      engine/train.py:115-121), on the device (loss.py)
+  PoseNet.pnp_backward, PoseNet.head_grads_pnp, pnp_grad
+                     the backward pass through the pose head ConvPnPNet (network/conv_pnp_net.py:18-201): from d pred_rot, d pred_t to
+                     the gradient of every pnp_net.* parameter and the head's part of d ivfc_coor, in fp32 on the device
+                     (pnp_grad.py, include/givepose_headgrad.h); the backward of the other modules is not part of this library
 """
 from .config import PoseNetConfig  # noqa: F401
 from .posenet import PoseNet  # noqa: F401

@@ -127,6 +127,34 @@ GRAD_PROTOTYPES = {
 }
 GPG_TERMS, GPG_SMALL, GPG_DECODE = 6, 15, 18
 
+
+# the pose-head backward family (include/givepose_headgrad.h, prefix gph_; tests/test_pnp_backward_cpu.py checks both ways)
+class PnpParams(Structure):      # gph_pnp_params: the 23 tensors of pnp_net, weights or their gradients
+    FIELDS = (["conv_w"] * 3 + ["gn_w"] * 3 + ["gn_b"] * 3 + ["fc1_w", "fc1_b", "fc1z_w", "fc1z_b", "fc2_w", "fc2_b", "fc2z_w", "fc2z_b",
+                                                             "fcr_w", "fcr_b", "fct_w", "fct_b", "fcz_w", "fcz_b"])
+    _fields_ = [("conv_w", c_void_p * 3), ("gn_w", c_void_p * 3), ("gn_b", c_void_p * 3)] + [(n, c_void_p) for n in FIELDS[9:]]
+
+
+class PnpSaved(Structure):       # gph_pnp_saved
+    _fields_ = [("x0", c_void_p), ("conv", c_void_p * 3), ("mean", c_void_p * 3), ("rstd", c_void_p * 3), ("act", c_void_p * 3),
+                ("h1", c_void_p), ("h2", c_void_p), ("h2z", c_void_p), ("pred_rot", c_void_p), ("pred_t", c_void_p)]
+
+
+c_longlong = ctypes.c_longlong
+HEADGRAD_PROTOTYPES = {
+    "gph_linear_backward_workspace": ([c_int] * 3, c_longlong),
+    "gph_linear_backward": ([_P, c_int, _P, c_int, _P, _P] + [c_int] * 5 + [_P, c_int, _P, _P, _P, c_longlong, _P], c_int),
+    "gph_gn_relu_backward_workspace": ([c_int] * 2, c_longlong),
+    "gph_gn_relu_backward": ([_P] * 6 + [c_int] * 3 + [_P] * 4 + [c_longlong, _P], c_int),
+    "gph_conv3x3s2_backward_workspace": ([c_int] * 5, c_longlong),
+    "gph_conv3x3s2_backward": ([_P] * 4 + [c_int] * 5 + [_P] * 3 + [c_longlong, _P], c_int),
+    "gph_pnp_forward_workspace": ([c_int] * 2, c_longlong),
+    "gph_pnp_forward_save": ([_P] * 3 + [POINTER(PnpParams), c_int, c_int, POINTER(PnpSaved), _P, c_longlong, _P], c_int),
+    "gph_pnp_backward_workspace": ([c_int] * 2, c_longlong),
+    "gph_pnp_backward": ([POINTER(PnpParams), POINTER(PnpSaved)] + [_P] * 3 + [c_int, c_int, POINTER(PnpParams), _P, _P, c_longlong, _P], c_int),
+}
+GPH_MAX_SPLIT, GPH_FEAT, GPH_GROUPS, GPH_RES = 8, 128, 32, 64
+
 _lib = None
 
 
@@ -145,7 +173,7 @@ def load():
             "There is no CPU or PyTorch fallback for the product path.")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (argtypes, restype) in (list(PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items())
-                                      + list(GRAD_PROTOTYPES.items())):
+                                      + list(GRAD_PROTOTYPES.items()) + list(HEADGRAD_PROTOTYPES.items())):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.argtypes = argtypes
         fn.restype = restype

@@ -113,6 +113,7 @@ class PoseNet(nn.Module):
                 aliases[key] = t
             _register(self, name, t, not is_buf)
         self._packed = None       # device-side packed weights
+        self._pnp_f32 = None      # device-side fp32 copies of the pnp_net parameters in the reference's layout (pnp_backward)
         self.inflight = int(inflight)   # batches the caller keeps in flight (forward_device slots)
         if self.inflight > 1 and os.environ.get("GP_PACKED_FP32") == "1":
             # the A/B build with packed fp32 VALU ops: v_pk_fma_f32 results of one kernel's waves come out wrong beside another
@@ -137,6 +138,7 @@ class PoseNet(nn.Module):
                     lib.gp_graph_destroy(plan["graph"])
                     plan["graph"] = None
         self._packed = None
+        self._pnp_f32 = None
         self._plans = OrderedDict()
 
     def __del__(self):
@@ -942,7 +944,8 @@ class PoseNet(nn.Module):
         -> {"loss": the six terms, "output": the dict of forward(do_loss=True), "grads": {"rot6d", "pred_t", "size", "nocs_coor",
         "ivfc_coor"}}: the gradient of sum_k gout[k] * term_k (gout None: the total loss) at the tensors the heads emit -- the
         ConvPnPNet rotation vector, pred_t, the size head's output (pred_size = head + norm_mean_size, so d head = d size) and
-        the two coordinate maps.  The backward pass through the network is not part of this library.
+        the two coordinate maps.  The backward pass stops at these tensors; `head_grads_pnp` carries it on through the pose head
+        (ConvPnPNet), and the backward of the other modules is not part of this library.
 
         For an r_type whose raw vector is not decoded by rot6d_to_mat_batch (kind != 0 in config.ROT_TYPES: the fixed-axis 6d
         forms, quaternion, Euler) grads["rot6d"] is the gradient of the (B,3,3) allocentric rotation matrix `rot_allo` instead."""
@@ -957,3 +960,74 @@ class PoseNet(nn.Module):
         return {"loss": terms, "output": out,
                 "grads": {"rot6d": d["rot6d"] if kind == 0 else d["rot_allo"], "pred_t": d["pred_t"], "size": g["size"],
                           "nocs_coor": g["nocs_coor"], "ivfc_coor": g["ivfc_coor"]}}
+
+    # ------------------------------------------------------------------ backward through the pose head
+    def _pnp_backward_supported(self, need_rot6d=False):
+        """ConvPnPNet with flat_op 'flatten' and mask_attention_type 'none' | 'mul' is what gph_pnp_backward differentiates."""
+        cfg = self.cfg
+        if cfg.pnp_head != "conv":
+            raise NotImplementedError(f"pnp_backward: pnp_head={cfg.pnp_head!r} -- only the ConvPnPNet head (pnp_head='conv') has a backward")
+        if cfg.flat_op != "flatten":
+            raise NotImplementedError(f"pnp_backward: flat_op={cfg.flat_op!r} -- only flat_op='flatten' has a backward (the pooled modes do not)")
+        if cfg.mask_attention_type not in ("none", "mul"):
+            raise NotImplementedError(f"pnp_backward: mask_attention_type={cfg.mask_attention_type!r} -- only 'none' and 'mul' have a backward")
+        if need_rot6d and ROT_TYPES[cfg.r_type][1] != 0:
+            raise NotImplementedError(f"head_grads_pnp: r_type={cfg.r_type!r} -- its raw vector is not decoded by rot6d_to_mat_batch, so head_grads "
+                                      "has the gradient of rot_allo, not of pred_rot, and there is nothing to feed the pose head's backward")
+
+    def _pnp_params_f32(self, device):
+        """The pnp_net parameters as fp32 device tensors in the reference's own layout, from the state_dict (never from the packed
+        fp16 / split-plane copies of the forward path).  The copies are kept until a parameter changes: the key holds every
+        parameter's storage and version counter, so an in-place update (an optimiser step) or a replaced tensor is seen at the
+        next call, whatever the module's dtype and device."""
+        from . import pnp_grad
+        device = torch.device(device)
+        sd = self.state_dict()
+        src = [sd["pnp_net." + k] for k in pnp_grad.PARAM_KEYS]
+        key = (device, tuple((t.data_ptr(), t._version) for t in src))
+        if self._pnp_f32 is None or self._pnp_f32[0] != key:
+            self._pnp_f32 = (key, {k: t.detach().to(device=device, dtype=torch.float32).contiguous() for k, t in zip(pnp_grad.PARAM_KEYS, src)})
+        return self._pnp_f32[1]
+
+    @torch.no_grad()
+    def pnp_backward(self, ivfc_coor, roi_coord_2d, g_pred_rot, g_pred_t, mask=None, device="cuda", return_saved=False):
+        """Backward of the pose head (ConvPnPNet, network/conv_pnp_net.py:137-201) in fp32 on the device: the head is recomputed in
+        fp32 from ivfc_coor (B,3,64,64) and roi_coord_2d (B,2,64,64) -- and mask (B,1,64,64), required with mask_attention_type='mul' and
+        ignored with 'none' -- saving what the backward needs (gph_pnp_forward_save), then differentiated at that point from
+        g_pred_rot (B,rot_dim) and g_pred_t (B,3) (gph_pnp_backward).
+        -> {"param_grads": {state_dict name: fp32 gradient in that parameter's own shape and layout} for the 23 pnp_net.* tensors,
+            "ivfc_coor": (B,3,64,64), the head's part of d ivfc_coor, "outputs": {"pred_rot", "pred_t"} of the fp32 recompute};
+        return_saved adds "saved", the saved activations (givepose_amd.pnp_grad.saved_shapes).
+        The weights are read at every call: a parameter updated in place between two calls is differentiated at its new value."""
+        from . import pnp_grad
+        self._pnp_backward_supported()
+        cfg = self.cfg
+        if cfg.mask_attention_type == "mul" and mask is None:
+            raise ValueError("pnp_backward: mask_attention_type='mul' needs the (B,1,64,64) mask")
+        dev = torch.device(device)
+        _lib.load()
+        m = None if cfg.mask_attention_type == "none" else torch.as_tensor(mask).to(dev)
+        P = self._pnp_params_f32(dev)
+        rot_dim = ROT_TYPES[cfg.r_type][0]
+        saved = pnp_grad.pnp_forward_save(torch.as_tensor(ivfc_coor).to(dev), torch.as_tensor(roi_coord_2d).to(dev), P, mask=m, rot_dim=rot_dim)
+        grads, g_ivfc = pnp_grad.pnp_backward(P, saved, torch.as_tensor(g_pred_rot).to(dev), torch.as_tensor(g_pred_t).to(dev), mask=m)
+        res = {"param_grads": {"pnp_net." + k: v for k, v in grads.items()}, "ivfc_coor": g_ivfc,
+               "outputs": {"pred_rot": saved["pred_rot"], "pred_t": saved["pred_t"]}}
+        if return_saved:
+            res["saved"] = saved
+        return res
+
+    @torch.no_grad()
+    def head_grads_pnp(self, data, pose_loss, device="cuda", gout=None, groups=None):
+        """`head_grads` carried on through the pose head: the same result, where grads["ivfc_coor"] is now the total -- the direct part
+        of the sp2d_coor term plus what comes back through pnp_net from d pred_rot and d pred_t (the reference does not detach the map,
+        network/PoseNet.py:195-197), added in that order --, grads["ivfc_coor_direct"] keeps the direct part, and "param_grads" holds
+        the gradient of every pnp_net.* parameter (`pnp_backward` on the forward's own ivfc_coor, roi_coord_2d and mask)."""
+        self._pnp_backward_supported(need_rot6d=True)
+        res = self.head_grads(data, pose_loss, device, gout=gout, groups=groups)
+        g, out = res["grads"], res["output"]
+        back = self.pnp_backward(out["ivfc_coor"], data["roi_coord_2d"], g["rot6d"], g["pred_t"], mask=out["mask"], device=device)
+        g["ivfc_coor_direct"] = g["ivfc_coor"]
+        g["ivfc_coor"] = g["ivfc_coor"] + back["ivfc_coor"]
+        res["param_grads"] = back["param_grads"]
+        return res
