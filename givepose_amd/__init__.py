@@ -19,10 +19,16 @@ Public surface mirrors the reference for this path:
   PoseNet.pnp_backward, PoseNet.head_grads_pnp, pnp_grad
                      the backward pass through the pose head ConvPnPNet (network/conv_pnp_net.py:18-201): from d pred_rot, d pred_t to
                      the gradient of every pnp_net.* parameter and the head's part of d ivfc_coor, in fp32 on the device
-                     (pnp_grad.py, include/givepose_headgrad.h); the backward of the other modules is not part of this library
+                     (pnp_grad.py, include/givepose_headgrad.h)
+  PoseNet.xyz_head_backward, PoseNet.head_grads_xyz, xyz_grad
+                     the backward pass through a coordinate head TopDownXyzHead (network/xyz_head.py:195-366; xyz_nocs_head or
+                     xyz_deform_head): from d coor to the gradient of every parameter of the head and of its input feature, in fp32
+                     on the device (xyz_grad.py, include/givepose_xyzgrad.h); head_grads_xyz carries head_grads_pnp on through
+                     xyz_deform_head.  The backward of the other modules is not part of this library
 """
 from .config import PoseNetConfig  # noqa: F401
 from .posenet import PoseNet  # noqa: F401
+from . import pnp_grad, xyz_grad  # noqa: F401  (ctypes wrappers only: the library is loaded at the first call)
 
 
 def dcnv3_forward(*args, **kwargs):

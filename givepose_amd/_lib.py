@@ -155,6 +155,38 @@ HEADGRAD_PROTOTYPES = {
 }
 GPH_MAX_SPLIT, GPH_FEAT, GPH_GROUPS, GPH_RES = 8, 128, 32, 64
 
+
+# the coordinate-head backward family (include/givepose_xyzgrad.h, prefix gpx_; tests/test_xyz_backward_cpu.py checks both ways)
+class XyzParams(Structure):      # gpx_xyz_params: the 23 tensors of a TopDownXyzHead, weights or their gradients
+    _fields_ = [("deconv_w", c_void_p), ("conv_w", c_void_p * 6), ("gn_w", c_void_p * 7), ("gn_b", c_void_p * 7), ("out_w", c_void_p),
+                ("out_b", c_void_p)]
+
+
+class XyzSaved(Structure):       # gpx_xyz_saved
+    _fields_ = [("pre", c_void_p * 7), ("mean", c_void_p * 7), ("rstd", c_void_p * 7), ("act", c_void_p * 7), ("up", c_void_p * 2),
+                ("coor", c_void_p)]
+
+
+XYZGRAD_PROTOTYPES = {
+    "gpx_conv3x3s1_workspace": ([c_int] * 4, c_longlong),
+    "gpx_conv3x3s1_forward": ([_P, _P] + [c_int] * 4 + [_P, _P, c_longlong, _P], c_int),
+    "gpx_conv3x3s1_backward": ([_P] * 3 + [c_int] * 4 + [_P] * 3 + [c_longlong, _P], c_int),
+    "gpx_deconv3x3s2_workspace": ([c_int] * 4, c_longlong),
+    "gpx_deconv3x3s2_forward": ([_P, _P] + [c_int] * 4 + [_P, _P, c_longlong, _P], c_int),
+    "gpx_deconv3x3s2_backward": ([_P] * 3 + [c_int] * 4 + [_P] * 3 + [c_longlong, _P], c_int),
+    "gpx_gn_gelu_backward_workspace": ([c_int] * 2, c_longlong),
+    "gpx_gn_gelu_backward": ([_P] * 6 + [c_int] * 4 + [_P] * 4 + [c_longlong, _P], c_int),
+    "gpx_upsample_bilinear2x_forward": ([_P] + [c_int] * 3 + [_P, _P], c_int),
+    "gpx_upsample_bilinear2x_backward": ([_P] + [c_int] * 3 + [_P, _P], c_int),
+    "gpx_conv1x1_backward_workspace": ([c_int] * 4, c_longlong),
+    "gpx_conv1x1_backward": ([_P] * 3 + [c_int] * 4 + [_P] * 4 + [c_longlong, _P], c_int),
+    "gpx_xyz_forward_workspace": ([c_int] * 3, c_longlong),
+    "gpx_xyz_forward_save": ([_P, POINTER(XyzParams)] + [c_int] * 3 + [POINTER(XyzSaved), _P, c_longlong, _P], c_int),
+    "gpx_xyz_backward_workspace": ([c_int] * 3, c_longlong),
+    "gpx_xyz_backward": ([POINTER(XyzParams), POINTER(XyzSaved), _P, _P] + [c_int] * 3 + [POINTER(XyzParams), _P, _P, c_longlong, _P], c_int),
+}
+GPX_FEAT, GPX_GROUPS, GPX_LAYERS = 256, 32, 7
+
 _lib = None
 
 
@@ -173,7 +205,8 @@ def load():
             "There is no CPU or PyTorch fallback for the product path.")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (argtypes, restype) in (list(PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items())
-                                      + list(GRAD_PROTOTYPES.items()) + list(HEADGRAD_PROTOTYPES.items())):
+                                      + list(GRAD_PROTOTYPES.items()) + list(HEADGRAD_PROTOTYPES.items())
+                                      + list(XYZGRAD_PROTOTYPES.items())):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.argtypes = argtypes
         fn.restype = restype

@@ -114,6 +114,7 @@ class PoseNet(nn.Module):
             _register(self, name, t, not is_buf)
         self._packed = None       # device-side packed weights
         self._pnp_f32 = None      # device-side fp32 copies of the pnp_net parameters in the reference's layout (pnp_backward)
+        self._xyz_f32 = {}        # head -> the same for a coordinate head (xyz_head_backward)
         self.inflight = int(inflight)   # batches the caller keeps in flight (forward_device slots)
         if self.inflight > 1 and os.environ.get("GP_PACKED_FP32") == "1":
             # the A/B build with packed fp32 VALU ops: v_pk_fma_f32 results of one kernel's waves come out wrong beside another
@@ -139,6 +140,7 @@ class PoseNet(nn.Module):
                     plan["graph"] = None
         self._packed = None
         self._pnp_f32 = None
+        self._xyz_f32 = {}
         self._plans = OrderedDict()
 
     def __del__(self):
@@ -927,11 +929,13 @@ class PoseNet(nn.Module):
                 "mask": out["mask"].clone(), "nocs_coor": out["nocs_coor"].clone(), "ivfc_coor": out["ivfc_coor"].clone()}
 
     def _forward_do_loss(self, data, device, groups):
-        """-> (the dict of forward(do_loss=True), the raw head outputs the pose was decoded from: pred_rot, pred_t, rot_allo)."""
+        """-> (the dict of forward(do_loss=True), the raw head outputs the pose was decoded from: pred_rot, pred_t, rot_allo, and
+        feat_cat (B,512,8,8) fp32 NCHW, the input of xyz_deform_head: cat(conv_feat256, nocs_feat), network/PoseNet.py:192-193)."""
         from . import loss
         cfg = self.cfg
         out = self.forward_device({**data, "roi_mask": data["roi_mask_deform"]}, device, groups=groups)
         raw = {k: out[k].clone() for k in ("pred_rot", "pred_t", "rot_allo")}
+        raw["feat_cat"] = out["feat_cat"].permute(0, 3, 1, 2).float().contiguous()
         rot, trans = loss.pose_decode_train(raw["pred_t"], raw["rot_allo"], data["cam_K"], data["bbox_center"], data["resize_ratio"],
                                             data["roi_wh"], t_site=cfg.t_type == "site", is_allo=ROT_TYPES[cfg.r_type][2], eps=1e-4)
         return {"rot": rot, "trans": trans, "size": out["size"].clone(), "mask": out["mask"].clone(),
@@ -945,10 +949,15 @@ class PoseNet(nn.Module):
         "ivfc_coor"}}: the gradient of sum_k gout[k] * term_k (gout None: the total loss) at the tensors the heads emit -- the
         ConvPnPNet rotation vector, pred_t, the size head's output (pred_size = head + norm_mean_size, so d head = d size) and
         the two coordinate maps.  The backward pass stops at these tensors; `head_grads_pnp` carries it on through the pose head
-        (ConvPnPNet), and the backward of the other modules is not part of this library.
+        (ConvPnPNet) and `head_grads_xyz` from there through xyz_deform_head; the backward of the other modules is not part of this
+        library.
 
         For an r_type whose raw vector is not decoded by rot6d_to_mat_batch (kind != 0 in config.ROT_TYPES: the fixed-axis 6d
         forms, quaternion, Euler) grads["rot6d"] is the gradient of the (B,3,3) allocentric rotation matrix `rot_allo` instead."""
+        return self._head_grads(data, pose_loss, device, gout, groups)[0]
+
+    def _head_grads(self, data, pose_loss, device, gout, groups):
+        """-> (what head_grads returns, the forward's raw tensors of _forward_do_loss)."""
         from . import loss
         cfg = self.cfg
         out, raw = self._forward_do_loss(data, device, groups)
@@ -959,7 +968,7 @@ class PoseNet(nn.Module):
                                             t_site=cfg.t_type == "site", is_allo=is_allo, eps=1e-4)
         return {"loss": terms, "output": out,
                 "grads": {"rot6d": d["rot6d"] if kind == 0 else d["rot_allo"], "pred_t": d["pred_t"], "size": g["size"],
-                          "nocs_coor": g["nocs_coor"], "ivfc_coor": g["ivfc_coor"]}}
+                          "nocs_coor": g["nocs_coor"], "ivfc_coor": g["ivfc_coor"]}}, raw
 
     # ------------------------------------------------------------------ backward through the pose head
     def _pnp_backward_supported(self, need_rot6d=False):
@@ -1023,11 +1032,79 @@ class PoseNet(nn.Module):
         of the sp2d_coor term plus what comes back through pnp_net from d pred_rot and d pred_t (the reference does not detach the map,
         network/PoseNet.py:195-197), added in that order --, grads["ivfc_coor_direct"] keeps the direct part, and "param_grads" holds
         the gradient of every pnp_net.* parameter (`pnp_backward` on the forward's own ivfc_coor, roi_coord_2d and mask)."""
+        return self._head_grads_pnp(data, pose_loss, device, gout, groups)[0]
+
+    def _head_grads_pnp(self, data, pose_loss, device, gout, groups):
         self._pnp_backward_supported(need_rot6d=True)
-        res = self.head_grads(data, pose_loss, device, gout=gout, groups=groups)
+        res, raw = self._head_grads(data, pose_loss, device, gout, groups)
         g, out = res["grads"], res["output"]
         back = self.pnp_backward(out["ivfc_coor"], data["roi_coord_2d"], g["rot6d"], g["pred_t"], mask=out["mask"], device=device)
         g["ivfc_coor_direct"] = g["ivfc_coor"]
         g["ivfc_coor"] = g["ivfc_coor"] + back["ivfc_coor"]
         res["param_grads"] = back["param_grads"]
+        return res, raw
+
+    # ------------------------------------------------------------------ backward through a coordinate head
+    _XYZ_HEADS = ("xyz_nocs_head", "xyz_deform_head")
+
+    def _xyz_params_f32(self, head, device):
+        """The parameters of one coordinate head as fp32 device tensors in the reference's own layout, from the state_dict, kept
+        until a parameter changes (keyed on storage and version counter, as _pnp_params_f32)."""
+        from . import xyz_grad
+        device = torch.device(device)
+        sd = self.state_dict()
+        src = [sd[f"{head}.{k}"] for k in xyz_grad.PARAM_KEYS]
+        key = (device, tuple((t.data_ptr(), t._version) for t in src))
+        hit = self._xyz_f32.get(head)
+        if hit is None or hit[0] != key:
+            hit = (key, {k: t.detach().to(device=device, dtype=torch.float32).contiguous() for k, t in zip(xyz_grad.PARAM_KEYS, src)})
+            self._xyz_f32[head] = hit
+        return hit[1]
+
+    @torch.no_grad()
+    def xyz_head_backward(self, head, feat, g_coor, device="cuda", return_saved=False):
+        """Backward of a coordinate head (TopDownXyzHead, network/xyz_head.py:195-366; head in {"xyz_nocs_head", "xyz_deform_head"}) in
+        fp32 on the device: the head is recomputed in fp32 from feat (B,Cin,8,8) -- Cin 1024 for xyz_nocs_head (the backbone feature),
+        512 for xyz_deform_head (feat_cat) --, saving what the backward needs (gpx_xyz_forward_save), then differentiated at that point
+        from g_coor (B,3,64,64) (gpx_xyz_backward).
+        -> {"param_grads": {state_dict name: fp32 gradient in that parameter's own shape and layout} for all 35 names of the head -- a
+            features.N.gn.* entry IS the tensor object of its features.N.norm.* entry, as in the reference, where the two names are one
+            Parameter with one .grad; there are 23 distinct tensors --,
+            "feat": (B,Cin,8,8), the gradient of the input feature, "outputs": {"coor": (B,3,64,64)} of the fp32 recompute};
+        return_saved adds "saved", the saved activations (givepose_amd.xyz_grad.saved_shapes).
+        The weights are read at every call: a parameter updated in place between two calls is differentiated at its new value."""
+        from . import xyz_grad
+        if head not in self._XYZ_HEADS:
+            raise ValueError(f"xyz_head_backward: head {head!r}, expected one of {self._XYZ_HEADS}")
+        dev = torch.device(device)
+        _lib.load()
+        P = self._xyz_params_f32(head, dev)
+        Cin = P["features.0.weight"].shape[0]
+        feat = torch.as_tensor(feat).to(dev)
+        if feat.dim() != 4 or feat.shape[1] != Cin or feat.shape[2] != feat.shape[3]:
+            raise ValueError(f"xyz_head_backward: feat {tuple(feat.shape)}, expected (B,{Cin},H0,H0)")
+        feat = feat.to(torch.float32).contiguous()
+        saved = xyz_grad.xyz_forward_save(feat, P)
+        grads, g_feat = xyz_grad.xyz_backward(P, saved, feat, torch.as_tensor(g_coor).to(dev))
+        pg = {f"{head}.{k}": v for k, v in grads.items()}
+        for alias, k in xyz_grad.ALIASES.items():
+            pg[f"{head}.{alias}"] = grads[k]
+        res = {"param_grads": pg, "feat": g_feat, "outputs": {"coor": saved["coor"]}}
+        if return_saved:
+            res["saved"] = saved
+        return res
+
+    @torch.no_grad()
+    def head_grads_xyz(self, data, pose_loss, device="cuda", gout=None, groups=None):
+        """`head_grads_pnp` carried on through xyz_deform_head: the same result, where "param_grads" also holds the gradient of every
+        xyz_deform_head.* parameter and grads gains "feat_cat" (B,512,8,8), the gradient of the head's input, and its halves (views of
+        its channels) "conv_feat256" = 0..255 and "nocs_feat" = 256..511 (network/PoseNet.py:192-193).  The upstream gradient is the
+        total grads["ivfc_coor"]; the input is the forward's own feat_cat in fp32 (`xyz_head_backward` on it).  xyz_nocs_head is not
+        part of the chain: nocs_feat feeds back into nocs_coor through MAPEncoder, whose backward is not part of this library."""
+        res, raw = self._head_grads_pnp(data, pose_loss, device, gout, groups)
+        back = self.xyz_head_backward("xyz_deform_head", raw["feat_cat"], res["grads"]["ivfc_coor"], device=device)
+        res["param_grads"].update(back["param_grads"])
+        g = res["grads"]
+        g["feat_cat"] = back["feat"]
+        g["conv_feat256"], g["nocs_feat"] = back["feat"][:, :256], back["feat"][:, 256:]
         return res
