@@ -24,11 +24,17 @@ Public surface mirrors the reference for this path:
                      the backward pass through a coordinate head TopDownXyzHead (network/xyz_head.py:195-366; xyz_nocs_head or
                      xyz_deform_head): from d coor to the gradient of every parameter of the head and of its input feature, in fp32
                      on the device (xyz_grad.py, include/givepose_xyzgrad.h); head_grads_xyz carries head_grads_pnp on through
-                     xyz_deform_head.  The backward of the other modules is not part of this library
+                     xyz_deform_head
+  PoseNet.map_encoder_backward, PoseNet.feat_reducer_backward, PoseNet.head_grads_feat, enc_grad
+                     the backward pass through the map encoder MAPEncoder with DCNv3 layers (network/conv_pnp_net.py:254-332): from
+                     d nocs_feat to the gradient of its 48 parameters and of the coordinate map, per coupling batch, in fp32 on the
+                     device (enc_grad.py, include/givepose_encgrad.h), and through feat_reducer; head_grads_feat carries
+                     head_grads_xyz on through both and xyz_nocs_head to the gradient at the backbone's output.  The backward of
+                     the backbone and of size_head, and of the 'att' / plain-conv encoders, is not part of this library
 """
 from .config import PoseNetConfig  # noqa: F401
 from .posenet import PoseNet  # noqa: F401
-from . import pnp_grad, xyz_grad  # noqa: F401  (ctypes wrappers only: the library is loaded at the first call)
+from . import enc_grad, pnp_grad, xyz_grad  # noqa: F401  (ctypes wrappers only: the library is loaded at the first call)
 
 
 def dcnv3_forward(*args, **kwargs):

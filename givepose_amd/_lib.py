@@ -187,6 +187,48 @@ XYZGRAD_PROTOTYPES = {
 }
 GPX_FEAT, GPX_GROUPS, GPX_LAYERS = 256, 32, 7
 
+
+# the map-encoder backward family (include/givepose_encgrad.h, prefix gpe_; tests/test_enc_backward_cpu.py checks both ways)
+class EncLayerParams(Structure):      # gpe_layer_params: the 16 tensors of one encoder layer, weights or their gradients
+    FIELDS = ("conv_w", "conv_b", "dw_w", "dw_b", "ln_w", "ln_b", "off_w", "off_b", "mask_w", "mask_b", "in_w", "in_b", "out_w", "out_b",
+              "gn_w", "gn_b")
+    _fields_ = [(n, c_void_p) for n in FIELDS]
+
+
+class EncParams(Structure):           # gpe_enc_params
+    _fields_ = [("layer", EncLayerParams * 3)]
+
+
+class EncLayerSaved(Structure):       # gpe_layer_saved
+    FIELDS = ("x", "xp", "dwout", "ln_mean", "ln_rstd", "x1", "offset", "mask", "y", "pre", "gn_mean", "gn_rstd", "act")
+    _fields_ = [(n, c_void_p) for n in FIELDS]
+
+
+class EncSaved(Structure):            # gpe_enc_saved
+    _fields_ = [("layer", EncLayerSaved * 3)]
+
+
+ENCGRAD_PROTOTYPES = {
+    "gpe_linear_workspace": ([c_int] * 3, c_longlong),
+    "gpe_linear_forward": ([_P] * 3 + [c_int] * 3 + [_P, _P, c_longlong, _P], c_int),
+    "gpe_linear_backward": ([_P] * 3 + [c_int] * 3 + [_P] * 4 + [c_longlong, _P], c_int),
+    "gpe_dwln_forward_save": ([_P] * 5 + [c_int] * 5 + [_P] * 5, c_int),
+    "gpe_dwln_backward_workspace": ([c_int] * 5, c_longlong),
+    "gpe_dwln_backward": ([_P] * 8 + [c_int] * 5 + [_P] * 6 + [c_longlong, _P], c_int),
+    "gpe_dcnv3_core_forward": ([_P] * 3 + [c_int] * 3 + [_P] * 3, c_int),
+    "gpe_dcnv3_core_backward": ([_P] * 4 + [c_int] * 3 + [_P] * 4, c_int),
+    "gpe_gn_relu_forward": ([_P] * 3 + [c_int] * 4 + [_P] * 4, c_int),
+    "gpe_gn_relu_backward_workspace": ([c_int] * 2, c_longlong),
+    "gpe_gn_relu_backward": ([_P] * 6 + [c_int] * 4 + [_P] * 4 + [c_longlong, _P], c_int),
+    "gpe_conv1x1_backward_workspace": ([c_int] * 4, c_longlong),
+    "gpe_conv1x1_backward": ([_P] * 3 + [c_int] * 4 + [_P] * 4 + [c_longlong, _P], c_int),
+    "gpe_map_encoder_forward_workspace": ([c_int] * 2, c_longlong),
+    "gpe_map_encoder_forward_save": ([_P, POINTER(EncParams), c_int, c_int, POINTER(EncSaved), _P, c_longlong, _P], c_int),
+    "gpe_map_encoder_backward_workspace": ([c_int] * 2, c_longlong),
+    "gpe_map_encoder_backward": ([POINTER(EncParams), POINTER(EncSaved), _P, _P, c_int, c_int, POINTER(EncParams), _P, _P, c_longlong, _P], c_int),
+}
+GPE_FEAT, GPE_DCN_GROUPS, GPE_DCN_CHANNELS, GPE_TAPS, GPE_GN_GROUPS, GPE_LAYERS = 256, 4, 64, 9, 32, 3
+
 _lib = None
 
 
@@ -206,7 +248,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (argtypes, restype) in (list(PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items())
                                       + list(GRAD_PROTOTYPES.items()) + list(HEADGRAD_PROTOTYPES.items())
-                                      + list(XYZGRAD_PROTOTYPES.items())):
+                                      + list(XYZGRAD_PROTOTYPES.items()) + list(ENCGRAD_PROTOTYPES.items())):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.argtypes = argtypes
         fn.restype = restype

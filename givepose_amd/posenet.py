@@ -115,6 +115,7 @@ class PoseNet(nn.Module):
         self._packed = None       # device-side packed weights
         self._pnp_f32 = None      # device-side fp32 copies of the pnp_net parameters in the reference's layout (pnp_backward)
         self._xyz_f32 = {}        # head -> the same for a coordinate head (xyz_head_backward)
+        self._enc_f32 = {}        # module -> the same for nocs_encoder / feat_reducer (map_encoder_backward, feat_reducer_backward)
         self.inflight = int(inflight)   # batches the caller keeps in flight (forward_device slots)
         if self.inflight > 1 and os.environ.get("GP_PACKED_FP32") == "1":
             # the A/B build with packed fp32 VALU ops: v_pk_fma_f32 results of one kernel's waves come out wrong beside another
@@ -141,6 +142,7 @@ class PoseNet(nn.Module):
         self._packed = None
         self._pnp_f32 = None
         self._xyz_f32 = {}
+        self._enc_f32 = {}
         self._plans = OrderedDict()
 
     def __del__(self):
@@ -936,6 +938,7 @@ class PoseNet(nn.Module):
         out = self.forward_device({**data, "roi_mask": data["roi_mask_deform"]}, device, groups=groups)
         raw = {k: out[k].clone() for k in ("pred_rot", "pred_t", "rot_allo")}
         raw["feat_cat"] = out["feat_cat"].permute(0, 3, 1, 2).float().contiguous()
+        raw["feat"] = out["feat"]      # NHWC (B,8,8,Cfeat), the backbone's output, in the forward's dtype
         rot, trans = loss.pose_decode_train(raw["pred_t"], raw["rot_allo"], data["cam_K"], data["bbox_center"], data["resize_ratio"],
                                             data["roi_wh"], t_site=cfg.t_type == "site", is_allo=ROT_TYPES[cfg.r_type][2], eps=1e-4)
         return {"rot": rot, "trans": trans, "size": out["size"].clone(), "mask": out["mask"].clone(),
@@ -949,8 +952,8 @@ class PoseNet(nn.Module):
         "ivfc_coor"}}: the gradient of sum_k gout[k] * term_k (gout None: the total loss) at the tensors the heads emit -- the
         ConvPnPNet rotation vector, pred_t, the size head's output (pred_size = head + norm_mean_size, so d head = d size) and
         the two coordinate maps.  The backward pass stops at these tensors; `head_grads_pnp` carries it on through the pose head
-        (ConvPnPNet) and `head_grads_xyz` from there through xyz_deform_head; the backward of the other modules is not part of this
-        library.
+        (ConvPnPNet), `head_grads_xyz` from there through xyz_deform_head and `head_grads_feat` through MAPEncoder, xyz_nocs_head
+        and feat_reducer to the backbone's output; the backward of the backbone and of size_head is not part of this library.
 
         For an r_type whose raw vector is not decoded by rot6d_to_mat_batch (kind != 0 in config.ROT_TYPES: the fixed-axis 6d
         forms, quaternion, Euler) grads["rot6d"] is the gradient of the (B,3,3) allocentric rotation matrix `rot_allo` instead."""
@@ -1099,12 +1102,121 @@ class PoseNet(nn.Module):
         """`head_grads_pnp` carried on through xyz_deform_head: the same result, where "param_grads" also holds the gradient of every
         xyz_deform_head.* parameter and grads gains "feat_cat" (B,512,8,8), the gradient of the head's input, and its halves (views of
         its channels) "conv_feat256" = 0..255 and "nocs_feat" = 256..511 (network/PoseNet.py:192-193).  The upstream gradient is the
-        total grads["ivfc_coor"]; the input is the forward's own feat_cat in fp32 (`xyz_head_backward` on it).  xyz_nocs_head is not
-        part of the chain: nocs_feat feeds back into nocs_coor through MAPEncoder, whose backward is not part of this library."""
+        total grads["ivfc_coor"]; the input is the forward's own feat_cat in fp32 (`xyz_head_backward` on it).  The chain stops at
+        feat_cat here: nocs_feat feeds back into nocs_coor through MAPEncoder, which `head_grads_feat` carries on."""
+        return self._head_grads_xyz(data, pose_loss, device, gout, groups)[0]
+
+    def _head_grads_xyz(self, data, pose_loss, device, gout, groups):
         res, raw = self._head_grads_pnp(data, pose_loss, device, gout, groups)
         back = self.xyz_head_backward("xyz_deform_head", raw["feat_cat"], res["grads"]["ivfc_coor"], device=device)
         res["param_grads"].update(back["param_grads"])
         g = res["grads"]
         g["feat_cat"] = back["feat"]
         g["conv_feat256"], g["nocs_feat"] = back["feat"][:, :256], back["feat"][:, 256:]
+        return res, raw
+
+    # ------------------------------------------------------------------ backward through the map encoder and to the backbone feature
+    def _enc_backward_supported(self, who):
+        """MAPEncoder with DCNv3 layers is what gpe_map_encoder_backward differentiates."""
+        cfg = self.cfg
+        if cfg.nocsmap_encoder != "conv":
+            raise NotImplementedError(f"{who}: nocsmap_encoder={cfg.nocsmap_encoder!r} -- only the convolutional MAPEncoder "
+                                      "(nocsmap_encoder='conv') has a backward, the transformer encoder ('att') does not")
+        if cfg.use_dcn != "dcnv3":
+            raise NotImplementedError(f"{who}: use_dcn={cfg.use_dcn!r} -- only the DCNv3 encoder (use_dcn='dcnv3') has a backward, the plain "
+                                      "3x3 stride-2 conv encoder does not")
+
+    def _module_params_f32(self, module, keys, device):
+        """{key: fp32 device tensor} of `module`'s parameters from the state_dict, kept until one changes (keyed on storage and version
+        counter, as _xyz_params_f32)."""
+        device = torch.device(device)
+        sd = self.state_dict()
+        src = [sd[f"{module}.{k}"] for k in keys]
+        key = (device, tuple((t.data_ptr(), t._version) for t in src))
+        hit = self._enc_f32.get(module)
+        if hit is None or hit[0] != key:
+            hit = (key, {k: t.detach().to(device=device, dtype=torch.float32).contiguous() for k, t in zip(keys, src)})
+            self._enc_f32[module] = hit
+        return hit[1]
+
+    def _enc_groups(self, B, groups):
+        """The coupling batches of a forward over B crops: `groups` as given, else the forward's rule (dcn_couple chunks)."""
+        if groups is not None:
+            return [int(g) for g in groups]
+        if self.dcn_couple and B > self.dcn_couple:
+            if B % self.dcn_couple:
+                raise ValueError(f"batch {B} is not a multiple of dcn_couple = {self.dcn_couple}")
+            return [self.dcn_couple] * (B // self.dcn_couple)
+        return [B]
+
+    @torch.no_grad()
+    def map_encoder_backward(self, coor, g_nocs_feat, groups=None, device="cuda", return_saved=False):
+        """Backward of the map encoder (MAPEncoder with DCNv3 layers, network/conv_pnp_net.py:254-332) in fp32 on the device: the
+        encoder is recomputed in fp32 from coor (B,3,R,R), R a multiple of 8 (64 in the network), saving what the backward needs
+        (gpe_map_encoder_forward_save), then differentiated at that point from g_nocs_feat (B,256,R/8,R/8) (gpe_map_encoder_backward).
+        groups: the coupling batches -- the crops whose DCNv3 layers shared one flat offset / mask buffer in the forward that ran
+        (SURVEY.md 0.3); None is the forward's own rule: chunks of dcn_couple if that is set and B exceeds it, else one batch.
+        -> {"param_grads": {state_dict name: fp32 gradient in that parameter's own shape} for the 48 differentiated nocs_encoder.*
+            tensors (features.N.dcnv3.bn.* is never applied and has no entry, as its .grad stays None in the reference),
+            "coor": (B,3,R,R), the gradient of the map, "outputs": {"nocs_feat": (B,256,R/8,R/8)} of the fp32 recompute};
+        return_saved adds "saved", the list of the batches' saved activations (givepose_amd.enc_grad.saved_shapes).
+        d xp is scattered with fp32 atomics: two calls agree to rounding, not bit for bit (include/givepose_encgrad.h)."""
+        from . import enc_grad
+        self._enc_backward_supported("map_encoder_backward")
+        dev = torch.device(device)
+        _lib.load()
+        P = self._module_params_f32("nocs_encoder", enc_grad.PARAM_KEYS, dev)
+        coor = torch.as_tensor(coor).to(dev).to(torch.float32).contiguous()
+        groups = self._enc_groups(coor.shape[0], groups)
+        saved = enc_grad.enc_forward_save(coor, P, groups=groups)
+        grads, g_coor = enc_grad.enc_backward(P, saved, coor, torch.as_tensor(g_nocs_feat).to(dev))
+        res = {"param_grads": {"nocs_encoder." + k: v for k, v in grads.items()}, "coor": g_coor,
+               "outputs": {"nocs_feat": torch.cat([s["act"][2] for s in saved])}}
+        if return_saved:
+            res["saved"] = saved
+        return res
+
+    @torch.no_grad()
+    def feat_reducer_backward(self, feat, g_conv_feat256, device="cuda"):
+        """Backward of feat_reducer (a 1x1 conv with bias, Cfeat -> 256; network/PoseNet.py:191): feat (B,Cfeat,8,8) NCHW and
+        g_conv_feat256 (B,256,8,8) -> {"param_grads": {"feat_reducer.weight", "feat_reducer.bias"}, "feat": (B,Cfeat,8,8)}."""
+        from . import enc_grad
+        dev = torch.device(device)
+        _lib.load()
+        P = self._module_params_f32("feat_reducer", ("weight", "bias"), dev)
+        out = enc_grad.conv1x1_backward(torch.as_tensor(g_conv_feat256).to(dev), torch.as_tensor(feat).to(dev), P["weight"])
+        return {"param_grads": {"feat_reducer.weight": out["dW"], "feat_reducer.bias": out["db"]}, "feat": out["dX"]}
+
+    @torch.no_grad()
+    def head_grads_feat(self, data, pose_loss, device="cuda", gout=None, groups=None):
+        """`head_grads_xyz` carried on to the backbone's output: every entry the two share is the same bits, and
+          * "param_grads" also holds the gradient of feat_reducer.*, of the 48 differentiated nocs_encoder.* tensors and of all 35
+            names of xyz_nocs_head.*: every parameter outside the backbone and size_head;
+          * grads["nocs_coor_direct"] keeps the loss's own part of d nocs_coor, grads["nocs_coor_from_encoder"] is what comes back
+            through nocs_encoder from d nocs_feat (the reference does not detach the map, network/PoseNet.py:191-194) and
+            grads["nocs_coor"] becomes the total: the two added in that order;
+          * grads gains "feat_from_reducer" (feat_reducer's backward of d conv_feat256), "feat_from_nocs_head" (xyz_nocs_head's backward
+            of the total d nocs_coor) and "feat", their sum in that order: (B,Cfeat,8,8) NCHW, the gradient at the backbone's output.
+        The size head's contribution to d feat is NOT included: in train mode its BatchNorm1d normalises with batch statistics and
+        its Dropout is random, neither of which the eval-mode forward of this library computes, so a gradient at the forward that
+        ran would not be the reference's.  The backward of the backbone is not part of this library.
+        The inputs are the forward's own tensors in fp32 (nocs_coor, and feat, which the forward keeps NHWC); `groups` is used for the
+        forward and for the encoder's backward alike."""
+        self._enc_backward_supported("head_grads_feat")
+        res, raw = self._head_grads_xyz(data, pose_loss, device, gout, groups)
+        g, out = res["grads"], res["output"]
+        if raw["feat"] is None:
+            raise NotImplementedError(f"head_grads_feat: main_backbone={self.cfg.main_backbone!r} -- the forward returns the backbone's "
+                                      "output for the ConvNeXt backbone only")
+        B = out["nocs_coor"].shape[0]
+        enc =self.map_encoder_backward(out["nocs_coor"], g["nocs_feat"], groups=self._enc_groups(B, groups), device=device)
+        g["nocs_coor_direct"], g["nocs_coor_from_encoder"] = g["nocs_coor"], enc["coor"]
+        g["nocs_coor"] = g["nocs_coor"] + enc["coor"]
+        feat = raw["feat"].permute(0, 3, 1, 2).float().contiguous()
+        red = self.feat_reducer_backward(feat, g["conv_feat256"], device=device)
+        head = self.xyz_head_backward("xyz_nocs_head", feat, g["nocs_coor"], device=device)
+        for part in (red, enc, head):
+            res["param_grads"].update(part["param_grads"])
+        g["feat_from_reducer"], g["feat_from_nocs_head"] = red["feat"], head["feat"]
+        g["feat"] = red["feat"] + head["feat"]
         return res
