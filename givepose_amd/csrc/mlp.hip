@@ -765,8 +765,9 @@ extern "C" int gp_convnext_mlp(const void* x, const void* w1, const float* b1, c
     GP_REQUIRE(dtype == GP_F16, "gp_convnext_mlp: fp16 storage only (fp32 runs fc1 / fc2 through gp_gemm)");
     GP_REQUIRE(!s32 || (C == 128 && gp_gelu16_enabled()), "gp_convnext_mlp: GP_MLP_S32 exists for C = 128 with the packed-fp16 GELU");
     GP_REQUIRE(C == 128 || C == 256 || C == 512, "gp_convnext_mlp: C=%d must be 128, 256 or 512", C);
-    GP_REQUIRE(x && w1 && b1 && w2p && b2 && gamma && residual && out, "gp_convnext_mlp: null operand");
+    // (M before the pointers: an empty activation tensor has a null data pointer, and "M=0" is the message that names the mistake)
     GP_REQUIRE(M > 0 && M % (C == 512 ? 128 : 256) == 0, "gp_convnext_mlp: M=%ld must be a positive multiple of %d", M, C == 512 ? 128 : 256);
+    GP_REQUIRE(x && w1 && b1 && w2p && b2 && gamma && residual && out, "gp_convnext_mlp: null operand");
     GP_REQUIRE((((size_t)x | (size_t)w1 | (size_t)w2p | (size_t)residual | (size_t)out | (size_t)b1 | (size_t)b2 | (size_t)gamma) & 15) == 0,
                "gp_convnext_mlp: operands must be 16-byte aligned");
     GP_REQUIRE(x != out, "gp_convnext_mlp: x and out must not alias (out may alias residual)");

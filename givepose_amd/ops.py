@@ -388,17 +388,32 @@ MLP_S32 = 0x400        # include/givepose_hip.h GP_MLP_S32
 
 def convnext_mlp_pack_w2(w2, s32=False):
     """fc2.weight (C, 4C) fp16 -> the column order gp_convnext_mlp reads (include/givepose_hip.h); s32: the order of its 32x32x16-MFMA form."""
+    _contig(_chk(w2, "w2", torch.float16), "w2")
+    if w2.dim() != 2 or w2.shape[1] != 4 * w2.shape[0]:
+        raise RuntimeError(f"w2: expected shape (C, 4C), got {tuple(w2.shape)}")
     out = torch.empty_like(w2)
     fn = _L().gp_convnext_mlp_pack_w2_s32 if s32 else _L().gp_convnext_mlp_pack_w2
-    check(fn(_ptr(_contig(w2, "w2")), _ptr(out), w2.shape[0], _stream()), "gp_convnext_mlp_pack_w2")
+    check(fn(_ptr(w2), _ptr(out), w2.shape[0], _stream()), "gp_convnext_mlp_pack_w2")
     return out
 
 
 def convnext_mlp(x, w1, b1, w2p, b2, gamma, residual, out, s32=False):
-    """out = residual + gamma * fc2(GELU(fc1(x))) in one launch (fp16, C in {128, 256}); out may alias residual.  s32: w2p was packed with s32=True."""
+    """out = residual + gamma * fc2(GELU(fc1(x))) in one launch (fp16 tensors, fp32 b1 / b2 / gamma; C in {128, 256, 512}, M a multiple
+    of 256 -- of 128 for C = 512); out may alias residual, not x.  s32: w2p was packed with s32=True (C = 128 only).  Every operand is
+    checked here for device, dtype, shape and contiguity: the library takes raw pointers."""
+    _chk(x, "x", torch.float16)
+    if x.dim() != 2:
+        raise RuntimeError(f"x: expected shape (M, C), got {tuple(x.shape)}")
     M, C = x.shape
-    check(_L().gp_convnext_mlp(_ptr(_contig(x, "x")), _ptr(w1), _ptr(b1), _ptr(w2p), _ptr(b2), _ptr(gamma), _ptr(residual),
-                               _ptr(out), M, C, dtype_code(x.dtype) | (MLP_S32 if s32 else 0), _stream()), "gp_convnext_mlp")
+    for t, name, dt, shape in ((x, "x", torch.float16, (M, C)), (w1, "w1", torch.float16, (4 * C, C)), (b1, "b1", torch.float32, (4 * C,)),
+                               (w2p, "w2p", torch.float16, (C, 4 * C)), (b2, "b2", torch.float32, (C,)), (gamma, "gamma", torch.float32, (C,)),
+                               (residual, "residual", torch.float16, (M, C)), (out, "out", torch.float16, (M, C))):
+        _chk(t, name, dt)
+        if tuple(t.shape) != shape:
+            raise RuntimeError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
+        _contig(t, name)
+    check(_L().gp_convnext_mlp(_ptr(x), _ptr(w1), _ptr(b1), _ptr(w2p), _ptr(b2), _ptr(gamma), _ptr(residual),
+                               _ptr(out), M, C, GP_F16 | (MLP_S32 if s32 else 0), _stream()), "gp_convnext_mlp")
     return out
 
 

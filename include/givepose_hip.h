@@ -209,7 +209,8 @@ int gp_split_planes(const float* x, void* planes, long rows, int cols, long ldx,
  *   fragment that the GELU output forms in registers).  M % 256 == 0; all pointers 16-byte aligned.
  *   The GELU runs on packed fp16 arithmetic (common.hpp gelu16_slice) unless the environment has GP_GELU16=0. */
 int gp_convnext_mlp_pack_w2(const void* w2, void* w2p, int C, void* stream);
-/* round 6: the column order of the 32x32x16-MFMA form of gp_convnext_mlp (C = 128 / 256): pass GP_F16 | GP_MLP_S32 as `dtype` together with it */
+/* round 6: the column order of the 32x32x16-MFMA form of gp_convnext_mlp (packs C = 128 / 256; the kernel itself is built for C = 128 only and
+ * gp_convnext_mlp refuses GP_MLP_S32 with any other C, or with GP_GELU16=0): pass GP_F16 | GP_MLP_S32 as `dtype` together with it */
 int gp_convnext_mlp_pack_w2_s32(const void* w2, void* w2p, int C, void* stream);
 #define GP_MLP_S32 0x400
 int gp_convnext_mlp(const void* x, const void* w1, const float* b1, const void* w2p, const float* b2,

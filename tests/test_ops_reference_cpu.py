@@ -154,9 +154,9 @@ CLOSURE = {
     "gp_gemm": "tests/test_gemm_conformance.py::test_gemm_conformance",
     "gp_gemm_gn_rows": H + "test_gemm_small_m_latency_variant",
     "gp_split_planes": "tests/test_split_gemm.py::test_split_planes_reconstruct",
-    "gp_convnext_mlp_pack_w2": H + "test_convnext_mlp_fused",
-    "gp_convnext_mlp_pack_w2_s32": H + "test_convnext_mlp_fused_s32_form",
-    "gp_convnext_mlp": H + "test_convnext_mlp_fused",
+    "gp_convnext_mlp_pack_w2": "tests/test_mlp_conformance_gpu.py::test_pack_w2_bit_exact",
+    "gp_convnext_mlp_pack_w2_s32": "tests/test_mlp_conformance_gpu.py::test_pack_w2_bit_exact",
+    "gp_convnext_mlp": "tests/test_mlp_conformance_gpu.py::test_mlp_conformance",
     "gp_convnext_stem": H + "test_stem",
     "gp_dwconv_ln": NC + "test_dwconv_ln",
     "gp_dwconv_ln_groups": M + "test_dwconv_ln_groups",
