@@ -29,12 +29,17 @@ Public surface mirrors the reference for this path:
                      the backward pass through the map encoder MAPEncoder with DCNv3 layers (network/conv_pnp_net.py:254-332): from
                      d nocs_feat to the gradient of its 48 parameters and of the coordinate map, per coupling batch, in fp32 on the
                      device (enc_grad.py, include/givepose_encgrad.h), and through feat_reducer; head_grads_feat carries
-                     head_grads_xyz on through both and xyz_nocs_head to the gradient at the backbone's output.  The backward of
-                     the backbone and of size_head, and of the 'att' / plain-conv encoders, is not part of this library
+                     head_grads_xyz on through both and xyz_nocs_head to the gradient at the backbone's output
+  PoseNet.backbone_backward, PoseNet.head_grads_backbone, bb_grad
+                     the backward pass through the ConvNeXt backbone (timm convnext_base as called by network/backbone.py:36-46):
+                     from d feat to the gradient of its 340 parameters and of the image crop, in fp32 on the device, without an
+                     atomic (bb_grad.py, include/givepose_bbgrad.h); head_grads_backbone carries head_grads_feat on through it.
+                     The backward of size_head, of the resnet34 backbone and of the 'att' / plain-conv encoders is not part of
+                     this library
 """
 from .config import PoseNetConfig  # noqa: F401
 from .posenet import PoseNet  # noqa: F401
-from . import enc_grad, pnp_grad, xyz_grad  # noqa: F401  (ctypes wrappers only: the library is loaded at the first call)
+from . import bb_grad, enc_grad, pnp_grad, xyz_grad  # noqa: F401  (ctypes wrappers only: the library is loaded at the first call)
 
 
 def dcnv3_forward(*args, **kwargs):

@@ -229,6 +229,35 @@ ENCGRAD_PROTOTYPES = {
 }
 GPE_FEAT, GPE_DCN_GROUPS, GPE_DCN_CHANNELS, GPE_TAPS, GPE_GN_GROUPS, GPE_LAYERS = 256, 4, 64, 9, 32, 3
 
+
+# the backbone backward family (include/givepose_bbgrad.h, prefix gpb_; tests/test_bb_backward_cpu.py checks both ways)
+class BbBlockParams(Structure):       # gpb_block_params: the 9 tensors of one ConvNeXt block in state_dict order
+    FIELDS = ("gamma", "dw_w", "dw_b", "ln_w", "ln_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b")
+    _fields_ = [(n, c_void_p) for n in FIELDS]
+
+
+_PP, _PI = POINTER(c_void_p), POINTER(c_int)
+BBGRAD_PROTOTYPES = {
+    "gpb_dw7_forward": ([_P] * 3 + [c_int] * 4 + [_P, _P], c_int),
+    "gpb_dw7_backward_workspace": ([c_int] * 4, c_longlong),
+    "gpb_dw7_backward": ([_P] * 3 + [c_int] * 4 + [_P] * 4 + [c_longlong, _P], c_int),
+    "gpb_layernorm_forward_save": ([_P] * 3 + [c_int] * 2 + [_P] * 4, c_int),
+    "gpb_layernorm_backward_workspace": ([c_int] * 2, c_longlong),
+    "gpb_layernorm_backward": ([_P] * 5 + [c_int] * 2 + [_P] * 4 + [c_longlong, _P], c_int),
+    "gpb_patch_conv_workspace": ([c_int] * 7, c_longlong),
+    "gpb_patch_conv_forward": ([_P] * 3 + [c_int] * 7 + [_P, _P, c_longlong, _P], c_int),
+    "gpb_patch_conv_backward": ([_P] * 3 + [c_int] * 7 + [_P] * 4 + [c_longlong, _P], c_int),
+    "gpb_block_workspace": ([c_int] * 4, c_longlong),
+    "gpb_block_forward_save": ([_P, POINTER(BbBlockParams)] + [c_int] * 4 + [_P] * 7 + [c_longlong, _P], c_int),
+    "gpb_block_backward": ([_P, _P, POINTER(BbBlockParams)] + [_P] * 5 + [c_int] * 4 + [POINTER(BbBlockParams), _P, _P, c_longlong, _P], c_int),
+    "gpb_param_count": ([_PI, c_int], c_int),
+    "gpb_backbone_forward_workspace": ([_PI, _PI] + [c_int] * 3, c_longlong),
+    "gpb_backbone_forward_save": ([_P, _PP, _PI, _PI] + [c_int] * 3 + [_PP, _P, _P, c_longlong, _P], c_int),
+    "gpb_backbone_backward_workspace": ([_PI, _PI] + [c_int] * 3, c_longlong),
+    "gpb_backbone_backward": ([_PP, _PP, _P, _P, _PI, _PI] + [c_int] * 3 + [_PP, _P, _P, c_longlong, _P], c_int),
+}
+GPB_MAX_STAGES, GPB_STEM_PATCH, GPB_DOWN_PATCH = 8, 4, 2
+
 _lib = None
 
 
@@ -248,7 +277,8 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (argtypes, restype) in (list(PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items())
                                       + list(GRAD_PROTOTYPES.items()) + list(HEADGRAD_PROTOTYPES.items())
-                                      + list(XYZGRAD_PROTOTYPES.items()) + list(ENCGRAD_PROTOTYPES.items())):
+                                      + list(XYZGRAD_PROTOTYPES.items()) + list(ENCGRAD_PROTOTYPES.items())
+                                      + list(BBGRAD_PROTOTYPES.items())):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.argtypes = argtypes
         fn.restype = restype

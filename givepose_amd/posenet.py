@@ -953,7 +953,8 @@ class PoseNet(nn.Module):
         ConvPnPNet rotation vector, pred_t, the size head's output (pred_size = head + norm_mean_size, so d head = d size) and
         the two coordinate maps.  The backward pass stops at these tensors; `head_grads_pnp` carries it on through the pose head
         (ConvPnPNet), `head_grads_xyz` from there through xyz_deform_head and `head_grads_feat` through MAPEncoder, xyz_nocs_head
-        and feat_reducer to the backbone's output; the backward of the backbone and of size_head is not part of this library.
+        and feat_reducer to the backbone's output and `head_grads_backbone` through the backbone to the image; the backward of size_head
+        is not part of this library.
 
         For an r_type whose raw vector is not decoded by rot6d_to_mat_batch (kind != 0 in config.ROT_TYPES: the fixed-axis 6d
         forms, quaternion, Euler) grads["rot6d"] is the gradient of the (B,3,3) allocentric rotation matrix `rot_allo` instead."""
@@ -1199,7 +1200,7 @@ class PoseNet(nn.Module):
             of the total d nocs_coor) and "feat", their sum in that order: (B,Cfeat,8,8) NCHW, the gradient at the backbone's output.
         The size head's contribution to d feat is NOT included: in train mode its BatchNorm1d normalises with batch statistics and
         its Dropout is random, neither of which the eval-mode forward of this library computes, so a gradient at the forward that
-        ran would not be the reference's.  The backward of the backbone is not part of this library.
+        ran would not be the reference's.  `head_grads_backbone` carries the chain on through the backbone.
         The inputs are the forward's own tensors in fp32 (nocs_coor, and feat, which the forward keeps NHWC); `groups` is used for the
         forward and for the encoder's backward alike."""
         self._enc_backward_supported("head_grads_feat")
@@ -1219,4 +1220,53 @@ class PoseNet(nn.Module):
             res["param_grads"].update(part["param_grads"])
         g["feat_from_reducer"], g["feat_from_nocs_head"] = red["feat"], head["feat"]
         g["feat"] = red["feat"] + head["feat"]
+        return res
+
+    # ------------------------------------------------------------------ backward through the backbone
+    def _backbone_backward_supported(self, who):
+        """The ConvNeXt backbone is what gpb_backbone_backward differentiates."""
+        if self.cfg.main_backbone != "convnext":
+            raise NotImplementedError(f"{who}: main_backbone={self.cfg.main_backbone!r} -- only the ConvNeXt backbone (main_backbone='convnext') "
+                                      "has a backward, the resnet34 throughput variant does not")
+
+    @torch.no_grad()
+    def backbone_backward(self, img, g_feat, device="cuda", return_saved=False):
+        """Backward of the ConvNeXt backbone (timm convnext_base as called by network/backbone.py:36-46) in fp32 on the device: the
+        backbone is recomputed in fp32 from img (B,3,S,S), S a multiple of 32 (256 in the network), saving what the backward needs
+        (gpb_backbone_forward_save), then differentiated at that point from g_feat (B,Cfeat,S/32,S/32) (gpb_backbone_backward).
+        drop_path is 0 and the backbone has neither BatchNorm nor Dropout: train mode computes this forward.
+        -> {"param_grads": {state_dict name: fp32 gradient in that parameter's own shape} for every backbone.* tensor, in state_dict
+            order, "img": (B,3,S,S), the gradient of the image, "outputs": {"feat": (B,Cfeat,S/32,S/32)} of the fp32 recompute};
+        return_saved adds "saved" (givepose_amd.bb_grad.saved_shapes: 176.7 MB per crop for ConvNeXt-Base at 256 x 256).
+        There is no atomic on this path: two calls give equal bits.  The fp32 parameters are cached as `_module_params_f32` caches them."""
+        from . import bb_grad
+        self._backbone_backward_supported("backbone_backward")
+        dev = torch.device(device)
+        _lib.load()
+        P = self._module_params_f32("backbone", bb_grad.PARAM_KEYS(self.cfg), dev)
+        img = torch.as_tensor(img).to(dev).to(torch.float32).contiguous()
+        g_feat = torch.as_tensor(g_feat).to(dev).to(torch.float32).contiguous()
+        saved, feat = bb_grad.backbone_forward_save(img, P, self.cfg)
+        grads, d_img = bb_grad.backbone_backward(P, saved, img, g_feat, self.cfg)
+        res = {"param_grads": {"backbone." + k: v for k, v in grads.items()}, "img": d_img, "outputs": {"feat": feat}}
+        if return_saved:
+            res["saved"] = saved
+        return res
+
+    @torch.no_grad()
+    def head_grads_backbone(self, data, pose_loss, device="cuda", gout=None, groups=None):
+        """`head_grads_feat` carried on through the backbone to the image: every entry the two share is the same bits, and
+          * "param_grads" also holds the gradient of every backbone.* parameter: with it every parameter outside size_head (and the
+            never-applied nocs_encoder.features.N.bn.*) has its gradient;
+          * grads gains "roi_img" (B,3,S,S), the gradient of the image crop.
+        The upstream gradient is grads["feat"].  The backbone is differentiated at its own fp32 recompute from data["roi_img"]
+        (`backbone_backward`), while the heads were differentiated at the forward's feat, which for an fp16 network is the fp16
+        forward's: the two agree to the forward's precision, not bit for bit.
+        The size head's contribution to d feat is NOT included, for the reason `head_grads_feat` gives."""
+        self._backbone_backward_supported("head_grads_backbone")
+        self._enc_backward_supported("head_grads_backbone")
+        res = self.head_grads_feat(data, pose_loss, device, gout=gout, groups=groups)
+        back = self.backbone_backward(data["roi_img"], res["grads"]["feat"], device=device)
+        res["param_grads"].update(back["param_grads"])
+        res["grads"]["roi_img"] = back["img"]
         return res
