@@ -36,10 +36,18 @@ Public surface mirrors the reference for this path:
                      atomic (bb_grad.py, include/givepose_bbgrad.h); head_grads_backbone carries head_grads_feat on through it.
                      The backward of size_head, of the resnet34 backbone and of the 'att' / plain-conv encoders is not part of
                      this library
+  Ranger, clip_grad_norm_, flat_and_anneal_lr, PoseNet.train_step, PoseNet.params_updated, optim
+                     what the training loop does after backward() (engine/train.py:117-129): clip_grad_norm_ with the 2-norm, one
+                     step of Ranger (tools/torch_utils/solver/ranger2020.py: RAdam + Lookahead + gradient centralisation) over all
+                     tensors in three launches, and the factor of the flat_and_anneal schedule
+                     (tools/torch_utils/solver/lr_scheduler.py:177-263), on the device (optim.py, include/givepose_optim.h);
+                     train_step runs head_grads_backbone and then the step.  Gradient accumulation, the all-reduce across ranks
+                     and a device-side repack of the forward's weights are not part of this library
 """
 from .config import PoseNetConfig  # noqa: F401
 from .posenet import PoseNet  # noqa: F401
-from . import bb_grad, enc_grad, pnp_grad, xyz_grad  # noqa: F401  (ctypes wrappers only: the library is loaded at the first call)
+from . import bb_grad, enc_grad, optim, pnp_grad, xyz_grad  # noqa: F401  (ctypes wrappers only: the library is loaded at the first call)
+from .optim import Ranger, clip_grad_norm_, flat_and_anneal_lr  # noqa: F401
 
 
 def dcnv3_forward(*args, **kwargs):

@@ -258,6 +258,25 @@ BBGRAD_PROTOTYPES = {
 }
 GPB_MAX_STAGES, GPB_STEM_PATCH, GPB_DOWN_PATCH = 8, 4, 2
 
+
+# the optimiser family (include/givepose_optim.h, prefix gpo_; tests/test_optim_cpu.py checks both ways)
+class OptTensor(Structure):           # gpo_tensor: one parameter of a step (device pointers, host table)
+    _fields_ = [(n, c_void_p) for n in ("p", "g", "m", "v", "slow")] + [("n", c_longlong), ("rows", c_int), ("row_len", c_int),
+                                                                         ("flags", c_int), ("step_lr", c_float)]
+
+
+class OptHyper(Structure):            # gpo_hyper
+    _fields_ = [(n, c_double) for n in ("beta1", "beta2", "eps", "alpha", "weight_decay", "max_norm")]
+
+
+OPTIM_PROTOTYPES = {
+    "gpo_ranger_step_workspace": ([POINTER(OptTensor), c_int], c_longlong),
+    "gpo_ranger_step": ([POINTER(OptTensor), c_int, POINTER(OptHyper), _P, _P, c_longlong, _P], c_int),
+    "gpo_clip_grad_norm_workspace": ([POINTER(OptTensor), c_int], c_longlong),
+    "gpo_clip_grad_norm": ([POINTER(OptTensor), c_int, c_float, _P, _P, c_longlong, _P], c_int),
+}
+GPO_CHUNK, GPO_STEP_LAUNCHES, GPO_CLIP_LAUNCHES, GPO_MAX_TENSORS, GPO_FLAG_RECTIFIED, GPO_FLAG_LOOKAHEAD = 4096, 3, 3, 65536, 1, 2
+
 _lib = None
 
 
@@ -278,7 +297,7 @@ def load():
     for name, (argtypes, restype) in (list(PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items())
                                       + list(GRAD_PROTOTYPES.items()) + list(HEADGRAD_PROTOTYPES.items())
                                       + list(XYZGRAD_PROTOTYPES.items()) + list(ENCGRAD_PROTOTYPES.items())
-                                      + list(BBGRAD_PROTOTYPES.items())):
+                                      + list(BBGRAD_PROTOTYPES.items()) + list(OPTIM_PROTOTYPES.items())):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.argtypes = argtypes
         fn.restype = restype

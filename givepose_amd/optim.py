@@ -1,0 +1,324 @@
+"""The optimiser family (include/givepose_optim.h, gpo_*): what the reference's training loop does after backward()
+(engine/train.py:117-129) -- clip_grad_norm_(parameters, max_norm), a step of Ranger (tools/torch_utils/solver/ranger2020.py: RAdam +
+Lookahead + gradient centralisation, built by tools/training_utils.py:build_optimizer) and the flat_and_anneal schedule
+(tools/torch_utils/solver/lr_scheduler.py:177-263).
+
+The step runs on the device in this library's HIP kernels, in _lib.GPO_STEP_LAUNCHES launches whatever the number of tensors; there is
+no CPU path.  The host computes the per-tensor step scalars (N_sma, step_size) in Python floats exactly as ranger2020.py:192-214 does and
+writes them, with the pointers, into a host table that the entry point sends to the device with one asynchronous copy.  Nothing comes back
+to the host.
+
+Gradients arrive as `param_grads`, {state_dict name: fp32 device tensor in the parameter's shape}: what PoseNet.head_grads_backbone
+returns.  A parameter registered under two names (ConvModule's .gn / .norm) is one parameter and is updated once.
+
+`flat_and_anneal_lr` is host arithmetic: the factor on the base rate at iteration `it`.
+"""
+import ctypes
+import math
+from bisect import bisect_right
+
+import numpy as np
+import torch
+
+from . import _lib
+from .pnp_grad import _default_alloc, _stream
+
+# gpo_tensor as a numpy record (checked against ctypes.sizeof(_lib.OptTensor) at the first table)
+_TENSOR = np.dtype([("p", "u8"), ("g", "u8"), ("m", "u8"), ("v", "u8"), ("slow", "u8"), ("n", "i8"), ("rows", "i4"), ("row_len", "i4"),
+                    ("flags", "i4"), ("step_lr", "f4")])
+_STATE_KEYS = ("exp_avg", "exp_avg_sq", "slow_buffer")
+
+
+def _describe(t):
+    if not torch.is_tensor(t):
+        return type(t).__name__
+    return f"{tuple(t.shape)} {t.dtype} on {t.device}{'' if t.is_contiguous() else ', not contiguous'}"
+
+
+def _check_grad(name, g, dev, shape=None):
+    if (not torch.is_tensor(g) or g.device != dev or g.dtype != torch.float32 or not g.is_contiguous()
+            or (shape is not None and tuple(g.shape) != tuple(shape))):
+        want = f" {tuple(shape)}" if shape is not None else ""
+        raise ValueError(f"param_grads[{name!r}]: {_describe(g)}, expected contiguous float32{want} on {dev}")
+    return g
+
+
+def _table_ptr(tab):
+    assert tab.dtype == _TENSOR and tab.flags.c_contiguous and _TENSOR.itemsize == ctypes.sizeof(_lib.OptTensor)
+    return tab.ctypes.data_as(ctypes.POINTER(_lib.OptTensor))
+
+
+def _gc_rows(shape, use_gc, gc_conv_only):
+    """(rows, row_len) of gradient centralisation for a tensor of `shape`, (0, 0) if it is not centralised: a row is one index of dim 0."""
+    if not use_gc or len(shape) <= (3 if gc_conv_only else 1):
+        return 0, 0
+    n = 1
+    for d in shape[1:]:
+        n *= int(d)
+    return int(shape[0]), n
+
+
+def radam_step_size(step, beta1, beta2, n_sma_threshold):
+    """-> (rectified, step_size) of RAdam at `step`, in Python floats as ranger2020.py:192-214 computes them."""
+    beta2_t = beta2 ** step
+    n_sma_max = 2 / (1 - beta2) - 1
+    n_sma = n_sma_max - 2 * step * beta2_t / (1 - beta2_t)
+    if n_sma > n_sma_threshold:
+        return True, math.sqrt((1 - beta2_t) * (n_sma - 4) / (n_sma_max - 4) * (n_sma - 2) / n_sma * n_sma_max / (n_sma_max - 2)) / (1 - beta1 ** step)
+    return False, 1.0 / (1 - beta1 ** step)
+
+
+class Ranger:
+    """Ranger over the distinct parameters of `model`, stepped on the device by gpo_ranger_step.
+
+    model: a module on a HIP device whose parameters are fp32 and contiguous.  The optimiser owns three flat fp32 device buffers
+    (exp_avg, exp_avg_sq, slow_buffer; every tensor starts at a multiple of 64 elements) and updates the parameters in place through
+    their pointers; a step ends with model.params_updated() if the model has one.
+    alloc(name, shape): optional hook that supplies the state buffers, the two device scalars and the workspace (default torch.empty).
+    `scalars` holds the gradients' total 2-norm and the clip coefficient of the last step, on the device."""
+
+    _require_device = True       # the table and the state-dict layout need no device: tests/test_optim_cpu.py builds them on the host
+
+    def __init__(self, model, lr=1e-3, alpha=0.5, k=6, N_sma_threshhold=5, betas=(0.95, 0.999), eps=1e-5, weight_decay=0, use_gc=True,
+                 gc_conv_only=False, gc_loc=True, alloc=None):
+        if not 0.0 <= alpha <= 1.0:
+            raise ValueError(f"Invalid slow update rate: {alpha}")
+        if not 1 <= k:
+            raise ValueError(f"Invalid lookahead steps: {k}")
+        if not lr > 0:
+            raise ValueError(f"Invalid Learning Rate: {lr}")
+        if not eps > 0:
+            raise ValueError(f"Invalid eps: {eps}")
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f"Invalid betas: {betas}")
+        if not gc_loc:
+            raise NotImplementedError("Ranger: gc_loc=False -- centralising the generalised gradient (after the division by sqrt(v)) is not "
+                                      "built; only gc_loc=True, centralising the gradient itself, is")
+        self.model = model
+        self.lr, self.alpha, self.k, self.N_sma_threshhold = float(lr), float(alpha), int(k), N_sma_threshhold
+        self.betas, self.eps, self.weight_decay = (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
+        self.use_gc, self.gc_conv_only, self.gc_loc = bool(use_gc), bool(gc_conv_only), True
+        self.params, self.param_names, self._index = [], [], {}
+        by_ptr = {}
+        for name, p in model.named_parameters(remove_duplicate=False):
+            if (self._require_device and p.device.type != "cuda") or p.dtype != torch.float32 or not p.is_contiguous() or p.numel() < 1:
+                raise ValueError(f"Ranger: parameter {name}: {_describe(p)}, expected a non-empty contiguous float32 tensor on a HIP device "
+                                 "(move the model to the device first)")
+            i = by_ptr.get(p.data_ptr())
+            if i is None:
+                i = by_ptr[p.data_ptr()] = len(self.params)
+                self.params.append(p)
+                self.param_names.append(name)
+            elif tuple(self.params[i].shape) != tuple(p.shape):
+                raise ValueError(f"Ranger: {name} and {self.param_names[i]} share storage but not a shape")
+            self._index[name] = i
+        if not self.params:
+            raise ValueError("Ranger: the model has no parameters")
+        if [id(p) for p in model.parameters()] != [id(p) for p in self.params]:
+            raise ValueError("Ranger: distinct Parameter objects of the model share storage")
+        self.device = self.params[0].device
+        if any(p.device != self.device for p in self.params):
+            raise ValueError("Ranger: the parameters lie on more than one device")
+        n = len(self.params)
+        self.steps = [0] * n
+        sizes = np.array([p.numel() for p in self.params], np.int64)
+        self._offsets = np.concatenate([[0], np.cumsum((sizes + 63) // 64 * 64)])
+        self._alloc = alloc or _default_alloc(self.device)
+        total = int(self._offsets[-1])
+        self._flat = {key: self._alloc(key, (total,)).zero_() for key in _STATE_KEYS}
+        self.scalars = self._alloc("scalars", (2,)).zero_()
+        self._ws = None
+        st = np.zeros(n, _TENSOR)
+        st["p"] = [p.data_ptr() for p in self.params]
+        for key, field in zip(_STATE_KEYS, ("m", "v", "slow")):
+            st[field] = self._flat[key].data_ptr() + 4 * self._offsets[:-1]
+        st["n"] = sizes
+        rows = [_gc_rows(p.shape, self.use_gc, self.gc_conv_only) for p in self.params]
+        st["rows"], st["row_len"] = [r[0] for r in rows], [r[1] for r in rows]
+        self._static = st
+        self._scalar_cache = {}
+
+    # ------------------------------------------------------------------ state
+    def _view(self, key, i):
+        o = int(self._offsets[i])
+        return self._flat[key][o:o + self.params[i].numel()].view(self.params[i].shape)
+
+    def state_dict(self):
+        """torch.optim.Optimizer's layout: state[i] for every parameter that has been stepped, i the index in model.parameters() order;
+        param_groups[0]["param_names"] names each index (the first of a shared parameter's names)."""
+        state = {i: {"step": s, **{key: self._view(key, i).clone() for key in _STATE_KEYS}} for i, s in enumerate(self.steps) if s > 0}
+        group = {"lr": self.lr, "alpha": self.alpha, "k": self.k, "step_counter": 0, "betas": self.betas, "N_sma_threshhold": self.N_sma_threshhold,
+                 "eps": self.eps, "weight_decay": self.weight_decay, "params": list(range(len(self.params))), "param_names": list(self.param_names)}
+        return {"state": state, "param_groups": [group]}
+
+    def load_state_dict(self, sd):
+        groups = sd["param_groups"]
+        if len(groups) != 1 or list(groups[0]["params"]) != list(range(len(self.params))):
+            raise ValueError(f"Ranger.load_state_dict: one parameter group over {len(self.params)} parameters is expected")
+        g = groups[0]
+        if "param_names" in g and list(g["param_names"]) != self.param_names:
+            bad = [(a, b) for a, b in zip(g["param_names"], self.param_names) if a != b][:3]
+            raise ValueError(f"Ranger.load_state_dict: the parameter names differ, first {bad}")
+        for i, s in sd["state"].items():
+            if not 0 <= int(i) < len(self.params):
+                raise ValueError(f"Ranger.load_state_dict: state index {i} out of range")
+            for key in _STATE_KEYS:
+                if tuple(s[key].shape) != tuple(self.params[int(i)].shape):
+                    raise ValueError(f"Ranger.load_state_dict: state[{i}][{key}] {tuple(s[key].shape)}, expected {tuple(self.params[int(i)].shape)}")
+        self.lr, self.alpha, self.k = float(g["lr"]), float(g["alpha"]), int(g["k"])
+        self.betas, self.eps, self.weight_decay = (float(g["betas"][0]), float(g["betas"][1])), float(g["eps"]), float(g["weight_decay"])
+        self.N_sma_threshhold = g["N_sma_threshhold"]
+        for key in _STATE_KEYS:
+            self._flat[key].zero_()
+        self.steps = [0] * len(self.params)
+        for i, s in sd["state"].items():
+            self.steps[int(i)] = int(s["step"])
+            for key in _STATE_KEYS:
+                self._view(key, int(i)).copy_(s[key])
+
+    # ------------------------------------------------------------------ the step
+    def _collect(self, param_grads):
+        """{parameter index: gradient} of the names in param_grads, aliases merged."""
+        grads = {}
+        for name, g in param_grads.items():
+            i = self._index.get(name)
+            if i is None:
+                raise ValueError(f"param_grads[{name!r}]: the model has no parameter of that name")
+            _check_grad(name, g, self.device, self.params[i].shape)
+            seen = grads.get(i)
+            if seen is not None and seen[1].data_ptr() != g.data_ptr() and not torch.equal(seen[1], g):
+                raise ValueError(f"param_grads[{name!r}] and param_grads[{seen[0]!r}] name one parameter but carry different gradients")
+            if seen is None:
+                grads[i] = (name, g)
+        return grads
+
+    def _scalars_of(self, step, lr):
+        key = (step, lr)
+        hit = self._scalar_cache.get(key)
+        if hit is None:
+            rect, size = radam_step_size(step, self.betas[0], self.betas[1], self.N_sma_threshhold)
+            flags = (_lib.GPO_FLAG_RECTIFIED if rect else 0) | (_lib.GPO_FLAG_LOOKAHEAD if step % self.k == 0 else 0)
+            if len(self._scalar_cache) > 64:
+                self._scalar_cache.clear()
+            hit = self._scalar_cache[key] = (flags, size * lr)
+        return hit
+
+    def _workspace(self, nbytes):
+        if self._ws is None or self._ws.numel() * 4 < nbytes:
+            self._ws = self._alloc("workspace", (max(int(nbytes) // 4, 64),))
+            assert self._ws.data_ptr() % 256 == 0, "workspace buffers must be 256-byte aligned"
+        return self._ws
+
+    @torch.no_grad()
+    def step(self, param_grads, clip_norm=None, lr=None):
+        """One step over the parameters that have an entry in param_grads; a parameter without one is skipped and its step count does
+        not advance (p.grad is None in the reference).  clip_norm: clip_grad_norm_'s max_norm over these gradients, applied inside the
+        update (the gradients themselves are not scaled).  lr: this call's learning rate (default: the optimiser's)."""
+        lr = self.lr if lr is None else float(lr)
+        if clip_norm is not None and not float(clip_norm) > 0:
+            raise ValueError(f"Ranger.step: clip_norm {clip_norm} must be positive (or None)")
+        grads = self._collect(param_grads)
+        if not grads:
+            return
+        active = sorted(grads)
+        L = _lib.load()
+        first = [i for i in active if self.steps[i] == 0]
+        if first:        # the reference creates a parameter's state at its first step: slow_buffer starts as a copy of the parameter
+            dst, src = [self._view("slow_buffer", i) for i in first], [self.params[i].detach() for i in first]
+            if hasattr(torch, "_foreach_copy_"):
+                torch._foreach_copy_(dst, src)
+            else:
+                for d, s in zip(dst, src):
+                    d.copy_(s)
+        tab = self._static[active]
+        tab["p"] = [self.params[i].data_ptr() for i in active]
+        tab["g"] = [grads[i][1].data_ptr() for i in active]
+        sc = []
+        for i in active:
+            self.steps[i] += 1
+            sc.append(self._scalars_of(self.steps[i], lr))
+        tab["flags"], tab["step_lr"] = [s[0] for s in sc], [s[1] for s in sc]
+        hyper = _lib.OptHyper(self.betas[0], self.betas[1], self.eps, self.alpha, self.weight_decay, float(clip_norm) if clip_norm is not None else 0.0)
+        ptr = _table_ptr(tab)
+        nbytes = L.gpo_ranger_step_workspace(ptr, len(active))
+        if nbytes <= 0:
+            _lib.check(-1, "gpo_ranger_step_workspace")
+        ws = self._workspace(nbytes)
+        with torch.cuda.device(self.device):
+            _lib.check(L.gpo_ranger_step(ptr, len(active), ctypes.byref(hyper), self.scalars.data_ptr(), ws.data_ptr(), ws.numel() * 4,
+                                         _stream(self.device)), "gpo_ranger_step")
+        if hasattr(self.model, "params_updated"):
+            self.model.params_updated()
+
+
+@torch.no_grad()
+def clip_grad_norm_(param_grads, max_norm, alloc=None):
+    """torch.nn.utils.clip_grad_norm_(., max_norm, norm_type=2) over the gradients of param_grads ({name: tensor}; one tensor under two
+    names counts once): scales them in place by min(1, max_norm / (norm + 1e-6)) on the device (gpo_clip_grad_norm) and returns the total
+    norm as a 0-d device tensor.  Nothing is copied to the host."""
+    if not float(max_norm) > 0:
+        raise ValueError(f"clip_grad_norm_: max_norm {max_norm} must be positive")
+    seen, dev = {}, None
+    for name, g in param_grads.items():
+        if not torch.is_tensor(g) or g.device.type != "cuda":
+            raise ValueError(f"param_grads[{name!r}]: {_describe(g)}, expected contiguous float32 on a HIP device")
+        dev = dev or g.device
+        _check_grad(name, g, dev)
+        if g.numel():
+            seen.setdefault(g.data_ptr(), g)
+    if not seen:
+        raise ValueError("clip_grad_norm_: no gradients")
+    tab = np.zeros(len(seen), _TENSOR)
+    tab["g"], tab["n"] = list(seen), [g.numel() for g in seen.values()]
+    L = _lib.load()
+    ptr = _table_ptr(tab)
+    nbytes = L.gpo_clip_grad_norm_workspace(ptr, len(tab))
+    if nbytes <= 0:
+        _lib.check(-1, "gpo_clip_grad_norm_workspace")
+    alloc = alloc or _default_alloc(dev)
+    ws = alloc("workspace", (max(int(nbytes) // 4, 64),))
+    scalars = alloc("scalars", (2,))
+    with torch.cuda.device(dev):
+        _lib.check(L.gpo_clip_grad_norm(ptr, len(tab), float(max_norm), scalars.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream(dev)),
+                   "gpo_clip_grad_norm")
+    return scalars[0]
+
+
+def flat_and_anneal_lr(it, total_iters, warmup_iters=0, warmup_factor=0.1, warmup_method="linear", anneal_point=0.72, anneal_method="cosine",
+                       target_lr_factor=0, poly_power=1.0, step_gamma=0.1, steps=(2 / 3.0, 8 / 9.0)):
+    """The factor on the base learning rate at iteration `it` of the flat_and_anneal schedule
+    (tools/torch_utils/solver/lr_scheduler.py:177-263, the lambda its LambdaLR wraps): warm-up, flat, then the anneal."""
+    if warmup_method not in ("constant", "linear"):
+        raise ValueError(f"Only 'constant' or 'linear' warmup_method accepted, got {warmup_method}")
+    if anneal_method not in ("cosine", "linear", "poly", "exp", "step", "none"):
+        raise ValueError(f"Only 'cosine', 'linear', 'poly', 'exp', 'step' or 'none' anneal_method accepted, got {anneal_method}")
+    if anneal_method == "step":
+        if any(s < warmup_iters / total_iters or s > 1 for s in steps):
+            raise ValueError(f"error in steps: {steps}. warmup_iters: {warmup_iters} total_iters: {total_iters}. "
+                             f"steps should be in ({warmup_iters / total_iters},1)")
+        if list(steps) != sorted(steps):
+            raise ValueError(f"steps {steps} is not in ascending order.")
+        anneal_start = steps[0] * total_iters        # anneal_point is ignored
+    else:
+        if anneal_point > 1 or anneal_point < 0:
+            raise ValueError(f"anneal_point should be in [0,1], got {anneal_point}")
+        anneal_start = anneal_point * total_iters
+    x = it
+    if x < warmup_iters:
+        if warmup_method == "linear":
+            a = float(x) / warmup_iters
+            return warmup_factor * (1 - a) + a
+        return warmup_factor
+    if x >= anneal_start:
+        if anneal_method == "step":
+            return step_gamma ** bisect_right([s * total_iters for s in steps], float(x))
+        if anneal_method == "cosine":
+            return target_lr_factor + 0.5 * (1 - target_lr_factor) * (1 + math.cos(math.pi * ((float(x) - anneal_start) / (total_iters - anneal_start))))
+        if anneal_method == "linear":
+            return target_lr_factor + (1 - target_lr_factor) * (total_iters - float(x)) / (total_iters - anneal_start)
+        if anneal_method == "poly":
+            return target_lr_factor + (1 - target_lr_factor) * ((total_iters - float(x)) / (total_iters - anneal_start)) ** poly_power
+        if anneal_method == "exp":
+            return max(target_lr_factor, 5e-3) ** ((float(x) - anneal_start) / (total_iters - anneal_start))
+        return 1
+    return 1

@@ -145,6 +145,17 @@ class PoseNet(nn.Module):
         self._enc_f32 = {}
         self._plans = OrderedDict()
 
+    def params_updated(self):
+        """Call after the parameters were changed through their storage (a kernel that writes through raw pointers, such as
+        givepose_amd.optim.Ranger.step, changes neither data_ptr nor the version counter the caches are keyed on): drops the packed
+        weights of the forward (`_packed`) and the fp32 copies of the backward (`_pnp_f32`, `_xyz_f32`, `_enc_f32`), so that the next
+        forward repacks from the state_dict and the next backward reads the parameters again.
+        The plans go too (`_reset_plans`): a plan is not only activation buffers -- its captured hipGraph holds raw pointers to the
+        packed weight tensors that are dropped here, and its buffers hold weight-derived rows (the position embeddings of the 'att'
+        heads, a_pos / p_pos, are copied from `_packed` when the plan is built).  The next forward rebuilds its plan, as after
+        load_state_dict."""
+        self._reset_plans()
+
     def __del__(self):
         try:
             self._reset_plans()
@@ -1269,4 +1280,24 @@ class PoseNet(nn.Module):
         back = self.backbone_backward(data["roi_img"], res["grads"]["feat"], device=device)
         res["param_grads"].update(back["param_grads"])
         res["grads"]["roi_img"] = back["img"]
+        return res
+
+    # ------------------------------------------------------------------ one training step
+    @torch.no_grad()
+    def train_step(self, data, pose_loss, optimizer, device="cuda", groups=None, clip_norm=5.0, lr=None):
+        """One iteration of the reference's loop (engine/train.py:113-129) for a single batch: `head_grads_backbone` (forward, the six
+        loss terms, the backward chain to the image), then optimizer.step(param_grads, clip_norm=clip_norm, lr=lr) with a
+        givepose_amd.optim.Ranger built over this model: clip_grad_norm_ at clip_norm (None: no clipping) fused into one Ranger step on
+        the device.  The step ends with `params_updated()`, so the next forward repacks the updated weights (on the host: `_pack`).
+        -> what `head_grads_backbone` returns (res["loss"] holds the six terms; the gradients in res["param_grads"] are left as computed,
+        not scaled by the clip coefficient, which is in optimizer.scalars[1] next to the norm in optimizer.scalars[0]).
+        The size head gets no gradient and is NOT updated, and neither are the never-applied nocs_encoder.features.N.dcnv3.bn.*: in train
+        mode the size head's BatchNorm1d normalises with batch statistics and its Dropout is random, neither of which the eval-mode
+        forward of this library computes (`head_grads_feat`), so its contribution to d feat is not included either.
+        Not built: gradient accumulation over several batches (accumulate > 1; the reference clips on every micro-step and steps on the
+        last) and the all-reduce of the gradients across ranks."""
+        if getattr(optimizer, "model", None) is not self:
+            raise ValueError("train_step: the optimizer must be a givepose_amd.optim.Ranger built over this model")
+        res = self.head_grads_backbone(data, pose_loss, device, groups=groups)
+        optimizer.step(res["param_grads"], clip_norm=clip_norm, lr=lr)
         return res
