@@ -34,8 +34,12 @@ Public surface mirrors the reference for this path:
                      the backward pass through the ConvNeXt backbone (timm convnext_base as called by network/backbone.py:36-46):
                      from d feat to the gradient of its 340 parameters and of the image crop, in fp32 on the device, without an
                      atomic (bb_grad.py, include/givepose_bbgrad.h); head_grads_backbone carries head_grads_feat on through it.
-                     The backward of size_head, of the resnet34 backbone and of the 'att' / plain-conv encoders is not part of
-                     this library
+                     The backward of the resnet34 backbone and of the 'att' / plain-conv encoders is not part of this library
+  PoseNet.size_head_backward, size_grad, and size_head={"seed": s} | {"keep": mask} of head_grads_feat / head_grads_backbone / train_step
+                     the size head as the training loop runs it (network/pose_head.py:17-42 under network.train()): BatchNorm1d on
+                     the statistics of the batch, Dropout(0.2) with an explicit or seeded mask, its backward to the six size_head.*
+                     parameters and to d feat, and the update of bn1's running statistics, in fp32 on the device without an atomic
+                     (size_grad.py, include/givepose_sizegrad.h)
   Ranger, clip_grad_norm_, flat_and_anneal_lr, PoseNet.train_step, PoseNet.params_updated, optim
                      what the training loop does after backward() (engine/train.py:117-129): clip_grad_norm_ with the 2-norm, one
                      step of Ranger (tools/torch_utils/solver/ranger2020.py: RAdam + Lookahead + gradient centralisation) over all
@@ -46,7 +50,7 @@ Public surface mirrors the reference for this path:
 """
 from .config import PoseNetConfig  # noqa: F401
 from .posenet import PoseNet  # noqa: F401
-from . import bb_grad, enc_grad, optim, pnp_grad, xyz_grad  # noqa: F401  (ctypes wrappers only: the library is loaded at the first call)
+from . import bb_grad, enc_grad, optim, pnp_grad, size_grad, xyz_grad  # noqa: F401  (ctypes wrappers only: the library is loaded at the first call)
 from .optim import Ranger, clip_grad_norm_, flat_and_anneal_lr  # noqa: F401
 
 

@@ -277,6 +277,28 @@ OPTIM_PROTOTYPES = {
 }
 GPO_CHUNK, GPO_STEP_LAUNCHES, GPO_CLIP_LAUNCHES, GPO_MAX_TENSORS, GPO_FLAG_RECTIFIED, GPO_FLAG_LOOKAHEAD = 4096, 3, 3, 65536, 1, 2
 
+
+
+# the train-mode size head (include/givepose_sizegrad.h, prefix gps_; tests/test_size_train_cpu.py checks both ways)
+class SizeParams(Structure):          # gps_params: size_head's six tensors, weights or their gradients
+    FIELDS = ("w1", "b1", "w2", "b2", "gamma", "beta")
+    _fields_ = [(n, c_void_p) for n in FIELDS]
+
+
+class SizeSaved(Structure):           # gps_saved
+    FIELDS = ("pooled", "arg", "h", "mean", "mean_lo", "rstd", "rstd_lo", "d", "keep", "out", "var_unbiased")
+    _fields_ = [(n, c_void_p) for n in FIELDS]
+
+
+c_ulonglong = ctypes.c_ulonglong
+SIZEGRAD_PROTOTYPES = {
+    "gps_size_forward_save": ([_P, c_int, c_int, POINTER(SizeParams), _P, c_ulonglong, _P] + [c_int] * 4 + [POINTER(SizeSaved), _P, _P], c_int),
+    "gps_size_backward_workspace": ([c_int] * 4, c_longlong),
+    "gps_size_backward": ([POINTER(SizeParams), POINTER(SizeSaved), _P] + [c_int] * 4 + [POINTER(SizeParams), _P, _P, c_longlong, _P], c_int),
+    "gps_bn_running_update": ([_P] * 5 + [c_int, c_double, _P], c_int),
+}
+GPS_CHUNK, GPS_MAX_C, GPS_FORWARD_LAUNCHES, GPS_BACKWARD_LAUNCHES, GPS_DROP_THRESHOLD = 4, 4096, 3, 3, 858993459
+
 _lib = None
 
 
@@ -297,7 +319,8 @@ def load():
     for name, (argtypes, restype) in (list(PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items())
                                       + list(GRAD_PROTOTYPES.items()) + list(HEADGRAD_PROTOTYPES.items())
                                       + list(XYZGRAD_PROTOTYPES.items()) + list(ENCGRAD_PROTOTYPES.items())
-                                      + list(BBGRAD_PROTOTYPES.items()) + list(OPTIM_PROTOTYPES.items())):
+                                      + list(BBGRAD_PROTOTYPES.items()) + list(OPTIM_PROTOTYPES.items())
+                                      + list(SIZEGRAD_PROTOTYPES.items())):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.argtypes = argtypes
         fn.restype = restype

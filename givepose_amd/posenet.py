@@ -12,6 +12,7 @@ Everything is channels-last on the device; the whole launch sequence of one forw
 in a hipGraph and replayed (``use_graph=True``).
 """
 import ctypes
+import functools
 import os
 from collections import OrderedDict
 
@@ -65,6 +66,24 @@ def _register(root, name, tensor, is_param):
 FUSE_GN_UPSAMPLE = os.environ.get("GP_FUSE_GN_UPSAMPLE", "1") != "0"
 
 _BUFFER_SUFFIXES = ("running_mean", "running_var", "num_batches_tracked")
+
+
+def _size_head_keyword(impl):
+    """Decorator of `head_grads_feat` and `head_grads_backbone`: the method also accepts the keyword-only option size_head= (None, the
+    default: the decorated method itself runs, as it always did; {"seed": s} or {"keep": mask}: checked, then `impl`, the method's
+    private form, runs with it).  The option is taken here and not in the `def` line because the chain's five methods -- head_grads,
+    head_grads_pnp, head_grads_xyz, head_grads_feat, head_grads_backbone -- keep one parameter list (data, pose_loss, device, gout,
+    groups), and the first three, which stop before `feat`, have no use for it: inspect.signature() shows that shared list, the docstrings
+    name the option."""
+    def deco(fn):
+        @functools.wraps(fn)
+        def method(self, *args, size_head=None, **kwargs):
+            if size_head is None:
+                return fn(self, *args, **kwargs)
+            self._size_head_mask(size_head, fn.__name__)
+            return getattr(self, impl)(*args, **kwargs, size_head=size_head)
+        return method
+    return deco
 
 
 class PoseNet(nn.Module):
@@ -964,26 +983,90 @@ class PoseNet(nn.Module):
         ConvPnPNet rotation vector, pred_t, the size head's output (pred_size = head + norm_mean_size, so d head = d size) and
         the two coordinate maps.  The backward pass stops at these tensors; `head_grads_pnp` carries it on through the pose head
         (ConvPnPNet), `head_grads_xyz` from there through xyz_deform_head and `head_grads_feat` through MAPEncoder, xyz_nocs_head
-        and feat_reducer to the backbone's output and `head_grads_backbone` through the backbone to the image; the backward of size_head
-        is not part of this library.
+        and feat_reducer to the backbone's output and `head_grads_backbone` through the backbone to the image.  The size head is
+        evaluated in eval mode here; `head_grads_feat` and what follows it take size_head= for the train-mode head and its backward.
 
         For an r_type whose raw vector is not decoded by rot6d_to_mat_batch (kind != 0 in config.ROT_TYPES: the fixed-axis 6d
         forms, quaternion, Euler) grads["rot6d"] is the gradient of the (B,3,3) allocentric rotation matrix `rot_allo` instead."""
         return self._head_grads(data, pose_loss, device, gout, groups)[0]
 
-    def _head_grads(self, data, pose_loss, device, gout, groups):
-        """-> (what head_grads returns, the forward's raw tensors of _forward_do_loss)."""
+    def _head_grads(self, data, pose_loss, device, gout, groups, size_head=None):
+        """-> (what head_grads returns, the forward's raw tensors of _forward_do_loss).  size_head ({"seed": s} or {"keep": mask}, from
+        `head_grads_feat`): the size head runs in TRAIN mode on the forward's feat before the loss (`_size_head_train`), output["size"] and
+        the Size term are taken at that prediction, raw gains "size_saved" and the result "size_head": {"outputs": {"size_raw", "keep"},
+        "stats": {"mean", "var_unbiased"}}."""
         from . import loss
         cfg = self.cfg
         out, raw = self._forward_do_loss(data, device, groups)
+        if size_head is not None:
+            raw["size_saved"] = self._size_head_train(raw["feat"], data["mean_size"], size_head, device)
+            out["size"] = raw["size_saved"]["size"]
         terms, g = pose_loss.value_and_grad(out, data, gout=gout)
         kind, is_allo = ROT_TYPES[cfg.r_type][1], ROT_TYPES[cfg.r_type][2]
         d = loss.pose_decode_train_backward(g["rot"], g["trans"], raw["pred_t"], raw["rot_allo"], data["cam_K"], data["bbox_center"],
                                             data["resize_ratio"], data["roi_wh"], rot6d=raw["pred_rot"] if kind == 0 else None,
                                             t_site=cfg.t_type == "site", is_allo=is_allo, eps=1e-4)
-        return {"loss": terms, "output": out,
-                "grads": {"rot6d": d["rot6d"] if kind == 0 else d["rot_allo"], "pred_t": d["pred_t"], "size": g["size"],
-                          "nocs_coor": g["nocs_coor"], "ivfc_coor": g["ivfc_coor"]}}, raw
+        res = {"loss": terms, "output": out,
+               "grads": {"rot6d": d["rot6d"] if kind == 0 else d["rot_allo"], "pred_t": d["pred_t"], "size": g["size"],
+                         "nocs_coor": g["nocs_coor"], "ivfc_coor": g["ivfc_coor"]}}
+        if size_head is not None:
+            sv = raw["size_saved"]
+            res["size_head"] = {"outputs": {"size_raw": sv["out"], "keep": sv["keep"]}, "stats": {"mean": sv["mean"], "var_unbiased": sv["var_unbiased"]}}
+        return res, raw
+
+    # ------------------------------------------------------------------ the size head in train mode
+    @staticmethod
+    def _size_head_mask(size_head, who):
+        """{"seed": s} or {"keep": mask} -> (keep, seed), one of them None."""
+        if not isinstance(size_head, dict) or set(size_head) - {"seed", "keep"}:
+            raise ValueError(f"{who}: size_head must be None, {{'seed': int}} or {{'keep': (B,F) uint8 mask}}, got {size_head!r}")
+        keep, seed = size_head.get("keep"), size_head.get("seed")
+        if (keep is None) == (seed is None):
+            raise ValueError(f"{who}: exactly one of keep and seed must be given")
+        return keep, seed
+
+    def _size_head_train(self, feat_nhwc, mean_size, size_head, device):
+        """The train-mode size head on the forward's own feat (NHWC, the forward's dtype, read in place) -> what size_forward_save saves,
+        with "size" = out + mean_size / |mean_size| (network/PoseNet.py:199-202)."""
+        from . import size_grad
+        keep, seed = self._size_head_mask(size_head, "size_head")
+        if feat_nhwc is None:
+            raise NotImplementedError(f"size_head: main_backbone={self.cfg.main_backbone!r} -- the forward returns the backbone's output for "
+                                      "the ConvNeXt backbone only")
+        dev = torch.device(device)
+        P = self._module_params_f32("size_head", size_grad.PARAM_KEYS, dev)
+        return size_grad.size_forward_save(feat_nhwc, P, keep=keep, seed=seed, nhwc=True, mean_size=torch.as_tensor(mean_size).to(dev))
+
+    @torch.no_grad()
+    def size_head_backward(self, feat, g_size, keep=None, seed=None, device="cuda", return_saved=False):
+        """Backward of the size head as the training loop runs it (SizeHead, network/pose_head.py:17-42, under network.train()): the head
+        is recomputed in fp32 from feat (B,C,H,W) in TRAIN mode -- max over the map (of equal maxima the lowest index takes the gradient),
+        conv1, BatchNorm1d on the statistics of these B crops (B >= 2), relu, Dropout(0.2), conv2 --, saving what the backward needs
+        (gps_size_forward_save), then differentiated at that point from g_size (B,3) (gps_size_backward; pred_size = head +
+        norm_mean_size, so d head = d size).
+        The dropout mask is an input, exactly one of: keep, a (B,F) uint8 tensor (non-zero = kept), or seed, an int in [0, 2^64) for
+        the counter-based rule of include/givepose_sizegrad.h (torch's generator cannot be matched).
+        -> {"param_grads": {state_dict name: fp32 gradient in that parameter's own shape} for the six size_head.* parameters,
+            "feat": (B,C,H,W), the gradient of the input feature (one non-zero per crop and channel),
+            "outputs": {"size_raw": (B,3) the head's output, "keep": (B,F) the mask that was used},
+            "stats": {"mean": (F,), "var_unbiased": (F,)}, what bn1.running_mean / running_var take (size_grad.bn_running_update)};
+        return_saved adds "saved" (givepose_amd.size_grad.saved_shapes).
+        No atomic: two calls give equal bits.  The weights are read at every call, as in `xyz_head_backward`."""
+        from . import size_grad
+        if (keep is None) == (seed is None):
+            raise ValueError("size_head_backward: exactly one of keep and seed must be given")
+        dev = torch.device(device)
+        _lib.load()
+        P = self._module_params_f32("size_head", size_grad.PARAM_KEYS, dev)
+        feat = torch.as_tensor(feat).to(dev).to(torch.float32).contiguous()
+        saved = size_grad.size_forward_save(feat, P, keep=keep, seed=seed)
+        grads, g_feat = size_grad.size_backward(P, saved, torch.as_tensor(g_size).to(dev), feat.shape)
+        res = {"param_grads": {"size_head." + k: v for k, v in grads.items()}, "feat": g_feat,
+               "outputs": {"size_raw": saved["out"], "keep": saved["keep"]},
+               "stats": {"mean": saved["mean"], "var_unbiased": saved["var_unbiased"]}}
+        if return_saved:
+            res["saved"] = saved
+        return res
 
     # ------------------------------------------------------------------ backward through the pose head
     def _pnp_backward_supported(self, need_rot6d=False):
@@ -1049,9 +1132,9 @@ class PoseNet(nn.Module):
         the gradient of every pnp_net.* parameter (`pnp_backward` on the forward's own ivfc_coor, roi_coord_2d and mask)."""
         return self._head_grads_pnp(data, pose_loss, device, gout, groups)[0]
 
-    def _head_grads_pnp(self, data, pose_loss, device, gout, groups):
+    def _head_grads_pnp(self, data, pose_loss, device, gout, groups, size_head=None):
         self._pnp_backward_supported(need_rot6d=True)
-        res, raw = self._head_grads(data, pose_loss, device, gout, groups)
+        res, raw = self._head_grads(data, pose_loss, device, gout, groups, size_head)
         g, out = res["grads"], res["output"]
         back = self.pnp_backward(out["ivfc_coor"], data["roi_coord_2d"], g["rot6d"], g["pred_t"], mask=out["mask"], device=device)
         g["ivfc_coor_direct"] = g["ivfc_coor"]
@@ -1118,8 +1201,8 @@ class PoseNet(nn.Module):
         feat_cat here: nocs_feat feeds back into nocs_coor through MAPEncoder, which `head_grads_feat` carries on."""
         return self._head_grads_xyz(data, pose_loss, device, gout, groups)[0]
 
-    def _head_grads_xyz(self, data, pose_loss, device, gout, groups):
-        res, raw = self._head_grads_pnp(data, pose_loss, device, gout, groups)
+    def _head_grads_xyz(self, data, pose_loss, device, gout, groups, size_head=None):
+        res, raw = self._head_grads_pnp(data, pose_loss, device, gout, groups, size_head)
         back = self.xyz_head_backward("xyz_deform_head", raw["feat_cat"], res["grads"]["ivfc_coor"], device=device)
         res["param_grads"].update(back["param_grads"])
         g = res["grads"]
@@ -1199,7 +1282,7 @@ class PoseNet(nn.Module):
         out = enc_grad.conv1x1_backward(torch.as_tensor(g_conv_feat256).to(dev), torch.as_tensor(feat).to(dev), P["weight"])
         return {"param_grads": {"feat_reducer.weight": out["dW"], "feat_reducer.bias": out["db"]}, "feat": out["dX"]}
 
-    @torch.no_grad()
+    @_size_head_keyword("_head_grads_feat")
     def head_grads_feat(self, data, pose_loss, device="cuda", gout=None, groups=None):
         """`head_grads_xyz` carried on to the backbone's output: every entry the two share is the same bits, and
           * "param_grads" also holds the gradient of feat_reducer.*, of the 48 differentiated nocs_encoder.* tensors and of all 35
@@ -1209,13 +1292,25 @@ class PoseNet(nn.Module):
             grads["nocs_coor"] becomes the total: the two added in that order;
           * grads gains "feat_from_reducer" (feat_reducer's backward of d conv_feat256), "feat_from_nocs_head" (xyz_nocs_head's backward
             of the total d nocs_coor) and "feat", their sum in that order: (B,Cfeat,8,8) NCHW, the gradient at the backbone's output.
-        The size head's contribution to d feat is NOT included: in train mode its BatchNorm1d normalises with batch statistics and
-        its Dropout is random, neither of which the eval-mode forward of this library computes, so a gradient at the forward that
-        ran would not be the reference's.  `head_grads_backbone` carries the chain on through the backbone.
+        Keyword-only option size_head= (`_size_head_keyword`).
+        size_head=None (the default): the size head's contribution to d feat is NOT included and size_head.* has no gradient -- in train
+        mode its BatchNorm1d normalises with batch statistics and its Dropout is random, neither of which the eval-mode forward computes,
+        so a gradient at the forward that ran would not be the reference's.
+        size_head={"seed": s} or {"keep": (B,F) uint8 mask}: the size head runs in TRAIN mode on the forward's feat before the loss
+        (batch-statistics BatchNorm1d, Dropout(0.2) with that mask: `size_head_backward`), output["size"] and the Size term are taken at
+        that prediction, and its backward is applied to grads["size"] (gps_size_backward on what the train-mode forward saved):
+        "param_grads" gains the six size_head.* entries, grads gains "feat_from_size_head", grads["feat"] is reducer + nocs head + size
+        head, added in that order, and the result gains "size_head": {"outputs": {"size_raw", "keep"}, "stats": {"mean",
+        "var_unbiased"}}.
+        `head_grads_backbone` carries the chain on through the backbone.
         The inputs are the forward's own tensors in fp32 (nocs_coor, and feat, which the forward keeps NHWC); `groups` is used for the
         forward and for the encoder's backward alike."""
+        return self._head_grads_feat(data, pose_loss, device, gout, groups)
+
+    @torch.no_grad()
+    def _head_grads_feat(self, data, pose_loss, device="cuda", gout=None, groups=None, size_head=None):
         self._enc_backward_supported("head_grads_feat")
-        res, raw = self._head_grads_xyz(data, pose_loss, device, gout, groups)
+        res, raw = self._head_grads_xyz(data, pose_loss, device, gout, groups, size_head)
         g, out = res["grads"], res["output"]
         if raw["feat"] is None:
             raise NotImplementedError(f"head_grads_feat: main_backbone={self.cfg.main_backbone!r} -- the forward returns the backbone's "
@@ -1231,6 +1326,13 @@ class PoseNet(nn.Module):
             res["param_grads"].update(part["param_grads"])
         g["feat_from_reducer"], g["feat_from_nocs_head"] = red["feat"], head["feat"]
         g["feat"] = red["feat"] + head["feat"]
+        if size_head is not None:
+            from . import size_grad
+            P = self._module_params_f32("size_head", size_grad.PARAM_KEYS, torch.device(device))
+            sgrads, sfeat = size_grad.size_backward(P, raw["size_saved"], g["size"], feat.shape)
+            res["param_grads"].update({"size_head." + k: v for k, v in sgrads.items()})
+            g["feat_from_size_head"] = sfeat
+            g["feat"] = g["feat"] + sfeat
         return res
 
     # ------------------------------------------------------------------ backward through the backbone
@@ -1264,7 +1366,7 @@ class PoseNet(nn.Module):
             res["saved"] = saved
         return res
 
-    @torch.no_grad()
+    @_size_head_keyword("_head_grads_backbone")
     def head_grads_backbone(self, data, pose_loss, device="cuda", gout=None, groups=None):
         """`head_grads_feat` carried on through the backbone to the image: every entry the two share is the same bits, and
           * "param_grads" also holds the gradient of every backbone.* parameter: with it every parameter outside size_head (and the
@@ -1273,10 +1375,16 @@ class PoseNet(nn.Module):
         The upstream gradient is grads["feat"].  The backbone is differentiated at its own fp32 recompute from data["roi_img"]
         (`backbone_backward`), while the heads were differentiated at the forward's feat, which for an fp16 network is the fp16
         forward's: the two agree to the forward's precision, not bit for bit.
-        The size head's contribution to d feat is NOT included, for the reason `head_grads_feat` gives."""
+        Keyword-only option size_head=, as in `head_grads_feat`.  With None the size head's contribution to d feat is NOT included, for the reason given there;
+        with a mask every parameter but the never-applied bn.* has its gradient and d feat is the reference's."""
+        return self._head_grads_backbone(data, pose_loss, device, gout, groups)
+
+    @torch.no_grad()
+    def _head_grads_backbone(self, data, pose_loss, device="cuda", gout=None, groups=None, size_head=None):
         self._backbone_backward_supported("head_grads_backbone")
         self._enc_backward_supported("head_grads_backbone")
-        res = self.head_grads_feat(data, pose_loss, device, gout=gout, groups=groups)
+        option = {} if size_head is None else {"size_head": size_head}
+        res = self.head_grads_feat(data, pose_loss, device, gout=gout, groups=groups, **option)
         back = self.backbone_backward(data["roi_img"], res["grads"]["feat"], device=device)
         res["param_grads"].update(back["param_grads"])
         res["grads"]["roi_img"] = back["img"]
@@ -1284,20 +1392,32 @@ class PoseNet(nn.Module):
 
     # ------------------------------------------------------------------ one training step
     @torch.no_grad()
-    def train_step(self, data, pose_loss, optimizer, device="cuda", groups=None, clip_norm=5.0, lr=None):
+    def train_step(self, data, pose_loss, optimizer, device="cuda", groups=None, clip_norm=5.0, lr=None, size_head=None):
         """One iteration of the reference's loop (engine/train.py:113-129) for a single batch: `head_grads_backbone` (forward, the six
         loss terms, the backward chain to the image), then optimizer.step(param_grads, clip_norm=clip_norm, lr=lr) with a
         givepose_amd.optim.Ranger built over this model: clip_grad_norm_ at clip_norm (None: no clipping) fused into one Ranger step on
         the device.  The step ends with `params_updated()`, so the next forward repacks the updated weights (on the host: `_pack`).
         -> what `head_grads_backbone` returns (res["loss"] holds the six terms; the gradients in res["param_grads"] are left as computed,
         not scaled by the clip coefficient, which is in optimizer.scalars[1] next to the norm in optimizer.scalars[0]).
-        The size head gets no gradient and is NOT updated, and neither are the never-applied nocs_encoder.features.N.dcnv3.bn.*: in train
-        mode the size head's BatchNorm1d normalises with batch statistics and its Dropout is random, neither of which the eval-mode
-        forward of this library computes (`head_grads_feat`), so its contribution to d feat is not included either.
+        The never-applied nocs_encoder.features.N.dcnv3.bn.* are not updated.  size_head=None (the default): the size head gets no
+        gradient and is NOT updated, and its contribution to d feat is not included (`head_grads_feat`).
+        size_head={"seed": s} or {"keep": mask}: the reference's iteration -- the size head runs in train mode, the Size term is taken at
+        its prediction, size_head.* is stepped with everything else, and after the optimiser step size_head.bn1.running_mean /
+        running_var / num_batches_tracked are updated on the device as nn.BatchNorm1d(momentum=0.1) updates them
+        (gps_bn_running_update), followed by `params_updated()`, so the next eval-mode forward folds the new statistics.  A fresh seed
+        per step is the caller's business.
         Not built: gradient accumulation over several batches (accumulate > 1; the reference clips on every micro-step and steps on the
         last) and the all-reduce of the gradients across ranks."""
         if getattr(optimizer, "model", None) is not self:
             raise ValueError("train_step: the optimizer must be a givepose_amd.optim.Ranger built over this model")
-        res = self.head_grads_backbone(data, pose_loss, device, groups=groups)
+        if size_head is not None:
+            self._size_head_mask(size_head, "train_step")
+        res = self.head_grads_backbone(data, pose_loss, device, groups=groups, **({} if size_head is None else {"size_head": size_head}))
         optimizer.step(res["param_grads"], clip_norm=clip_norm, lr=lr)
+        if size_head is not None:
+            from . import size_grad
+            sd, stats = self.state_dict(), res["size_head"]["stats"]
+            size_grad.bn_running_update(sd["size_head.bn1.running_mean"], sd["size_head.bn1.running_var"],
+                                        sd.get("size_head.bn1.num_batches_tracked"), stats["mean"], stats["var_unbiased"])
+            self.params_updated()      # the step's own call came before the buffers moved
         return res
