@@ -45,13 +45,17 @@ Public surface mirrors the reference for this path:
                      step of Ranger (tools/torch_utils/solver/ranger2020.py: RAdam + Lookahead + gradient centralisation) over all
                      tensors in three launches, and the factor of the flat_and_anneal schedule
                      (tools/torch_utils/solver/lr_scheduler.py:177-263), on the device (optim.py, include/givepose_optim.h);
-                     train_step runs head_grads_backbone and then the step.  Gradient accumulation, the all-reduce across ranks
-                     and a device-side repack of the forward's weights are not part of this library
+                     train_step runs head_grads_backbone and then the step.  A device-side repack of the forward's weights is not
+                     part of this library
+  GradAccumulator, train_step(accumulator=, accumulate=, micro_step=, group=)
+                     FLAGS.accumulate and the gradient all-reduce across ranks (engine/train.py:117-131): the micro-steps' gradients
+                     added, scaled and clipped in place in one flat device buffer in three launches, exchanged between ranks by one
+                     all_reduce, and stepped from by Ranger (optim.py, include/givepose_accum.h)
 """
 from .config import PoseNetConfig  # noqa: F401
 from .posenet import PoseNet  # noqa: F401
 from . import bb_grad, enc_grad, optim, pnp_grad, size_grad, xyz_grad  # noqa: F401  (ctypes wrappers only: the library is loaded at the first call)
-from .optim import Ranger, clip_grad_norm_, flat_and_anneal_lr  # noqa: F401
+from .optim import GradAccumulator, Ranger, clip_grad_norm_, flat_and_anneal_lr  # noqa: F401
 
 
 def dcnv3_forward(*args, **kwargs):

@@ -277,6 +277,13 @@ OPTIM_PROTOTYPES = {
 }
 GPO_CHUNK, GPO_STEP_LAUNCHES, GPO_CLIP_LAUNCHES, GPO_MAX_TENSORS, GPO_FLAG_RECTIFIED, GPO_FLAG_LOOKAHEAD = 4096, 3, 3, 65536, 1, 2
 
+# the gradient-accumulation family (include/givepose_accum.h, prefix gpc_; tests/test_grad_accum_cpu.py checks both ways)
+ACCUM_PROTOTYPES = {
+    "gpc_grad_accumulate_workspace": ([POINTER(OptTensor), c_int], c_longlong),
+    "gpc_grad_accumulate": ([POINTER(OptTensor), c_int, c_float, c_float, _P, _P, c_longlong, _P], c_int),
+}
+GPC_ACCUM_LAUNCHES, GPC_FLAG_OVERWRITE = 3, 4
+
 
 
 # the train-mode size head (include/givepose_sizegrad.h, prefix gps_; tests/test_size_train_cpu.py checks both ways)
@@ -320,7 +327,7 @@ def load():
                                       + list(GRAD_PROTOTYPES.items()) + list(HEADGRAD_PROTOTYPES.items())
                                       + list(XYZGRAD_PROTOTYPES.items()) + list(ENCGRAD_PROTOTYPES.items())
                                       + list(BBGRAD_PROTOTYPES.items()) + list(OPTIM_PROTOTYPES.items())
-                                      + list(SIZEGRAD_PROTOTYPES.items())):
+                                      + list(SIZEGRAD_PROTOTYPES.items()) + list(ACCUM_PROTOTYPES.items())):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.argtypes = argtypes
         fn.restype = restype

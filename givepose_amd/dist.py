@@ -4,7 +4,10 @@ The reference has no distributed code.  Crops are independent 
 DCNv3 stride-2 offset coupling, which stays inside one per-GPU batch, so the global batch is cut into
 contiguous shards (rank r owns [r*per, (r+1)*per)), every rank runs the same PoseNet replica, and the only
 exchange is ONE all-gather of (R 9, t 3, s 3) = 15 fp32 per crop over RCCL/xGMI (backend "nccl" on ROCm;
-"gloo" in the CPU tests).  No reduction exists on this path.
+"gloo" in the CPU tests).  The inference path has no reduction.  Training has one: the all_reduce of the flat
+gradient buffer of givepose_amd.optim.GradAccumulator (and, with the train-mode size head, the broadcast of
+bn1's running statistics from rank 0) in PoseNet.train_step(..., accumulator=, group=), over the process
+group that init_from_env creates.
 """
 import os
 

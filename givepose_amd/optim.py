@@ -12,6 +12,11 @@ Gradients arrive as `param_grads`, {state_dict name: fp32 device tensor in the p
 returns.  A parameter registered under two names (ConvModule's .gn / .norm) is one parameter and is updated once.
 
 `flat_and_anneal_lr` is host arithmetic: the factor on the base rate at iteration `it`.
+
+`GradAccumulator` (include/givepose_accum.h, gpc_*) is the loop's `.grad` when FLAGS.accumulate > 1 or more than one rank trains: one flat
+buffer in the layout of the optimiser's state, into which every micro-step's gradients are added and clipped in place in
+_lib.GPC_ACCUM_LAUNCHES launches, and which one all_reduce exchanges between ranks.  `rank_accum_selfcheck` is the rank worker of its
+multi-process tests.
 """
 import ctypes
 import math
@@ -282,6 +287,172 @@ def clip_grad_norm_(param_grads, max_norm, alloc=None):
         _lib.check(L.gpo_clip_grad_norm(ptr, len(tab), float(max_norm), scalars.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream(dev)),
                    "gpo_clip_grad_norm")
     return scalars[0]
+
+
+class GradAccumulator:
+    """The accumulated gradient of the reference's loop (engine/train.py:117-131 with FLAGS.accumulate, and DDP's gradient average) as one
+    flat fp32 device buffer in the layout of `optimizer`'s state buffers, filled by gpc_grad_accumulate (include/givepose_accum.h).
+
+    optimizer: a Ranger; the accumulator takes its parameters, names, aliases and offsets.  It owns
+      flat     the accumulated gradients, every tensor at a multiple of 64 elements; the padding is zeroed once and never written;
+      stage    a second buffer of the same size for the exchange between ranks, allocated at the first add() with a group;
+      scalars  the 2-norm of the accumulated gradients (before the clip) and the clip coefficient of the last add(), on the device.
+    alloc(name, shape): optional hook that supplies "flat", "stage", "scalars" and "workspace" (default torch.empty)."""
+
+    def __init__(self, optimizer, alloc=None):
+        if not isinstance(optimizer, Ranger):
+            raise ValueError(f"GradAccumulator: a givepose_amd.optim.Ranger is expected, got {type(optimizer).__name__}")
+        self.optimizer, self.device = optimizer, optimizer.device
+        self._offsets = optimizer._offsets
+        self._alloc = alloc or _default_alloc(self.device)
+        total = int(self._offsets[-1])
+        self.flat = self._alloc("flat", (total,)).zero_()
+        self.stage = None
+        self.scalars = self._alloc("scalars", (2,)).zero_()
+        self._ws = None
+        self._live = set()
+        self._staged = frozenset()
+        st = np.zeros(len(optimizer.params), _TENSOR)
+        st["p"] = self.flat.data_ptr() + 4 * self._offsets[:-1]
+        st["n"] = [p.numel() for p in optimizer.params]
+        self._static = st
+
+    def _view(self, i, buf=None):
+        o, p = int(self._offsets[i]), self.optimizer.params[i]
+        return (self.flat if buf is None else buf)[o:o + p.numel()].view(p.shape)
+
+    @property
+    def live(self):
+        """The names (aliases included) of the parameters that have an accumulated gradient since the last zero()."""
+        return [name for name, i in self.optimizer._index.items() if i in self._live]
+
+    @property
+    def grads(self):
+        """{name: view into flat} of the live parameters under every one of their names: what Ranger.step takes."""
+        return {name: self._view(i) for name, i in self.optimizer._index.items() if i in self._live}
+
+    def zero(self):
+        """optimizer.zero_grad(): no parameter has an accumulated gradient.  Nothing is written: the next add() overwrites."""
+        self._live = set()
+
+    def _workspace(self, nbytes):
+        if self._ws is None or self._ws.numel() * 4 < nbytes:
+            self._ws = self._alloc("workspace", (max(int(nbytes) // 4, 64),))
+            assert self._ws.data_ptr() % 256 == 0, "workspace buffers must be 256-byte aligned"
+        return self._ws
+
+    def _table(self, param_grads):
+        """-> (parameter indices, gpo_tensor table) of one add(): the parameters of param_grads and the live ones, in index order."""
+        grads = self.optimizer._collect(param_grads)
+        entries = sorted(set(grads) | self._live)
+        tab = self._static[entries]
+        tab["g"] = [grads[i][1].data_ptr() if i in grads else 0 for i in entries]
+        tab["flags"] = [_lib.GPC_FLAG_OVERWRITE if i not in self._live else 0 for i in entries]
+        return entries, tab, grads
+
+    def _launch(self, tab, scale, max_norm):
+        L = _lib.load()
+        ptr = _table_ptr(tab)
+        nbytes = L.gpc_grad_accumulate_workspace(ptr, len(tab))
+        if nbytes <= 0:
+            _lib.check(-1, "gpc_grad_accumulate_workspace")
+        ws = self._workspace(nbytes)
+        with torch.cuda.device(self.device):
+            _lib.check(L.gpc_grad_accumulate(ptr, len(tab), scale, max_norm, self.scalars.data_ptr(), ws.data_ptr(), ws.numel() * 4,
+                                             _stream(self.device)), "gpc_grad_accumulate")
+
+    def _world(self, group):
+        import torch.distributed as dist
+        return dist.get_world_size(group)
+
+    def _all_reduce(self, group):
+        """The one collective of an add(): the whole of `stage`, summed in place, on the current stream."""
+        import torch.distributed as dist
+        dist.all_reduce(self.stage, op=dist.ReduceOp.SUM, group=group)
+
+    @torch.no_grad()
+    def add(self, param_grads, scale=1.0, clip_norm=None, group=None):
+        """One micro-step: acc += scale * g for every entry of param_grads ({name: fp32 device tensor}, checked as Ranger.step checks
+        them), then clip_grad_norm_(., clip_norm) in place over ALL live parameters -- also those that are live but absent from
+        param_grads, which are counted in the norm and scaled (None: no clipping; scalars still receives the norm).  A parameter added
+        for the first time since zero() is overwritten.  A refused call changes nothing.  The entries are taken in parameter order.
+        group: a torch.distributed process group of `world` ranks: the gradients are first written to `stage` scaled by scale / world,
+        `stage` is summed over the ranks by ONE all_reduce on the current stream, and the sum is then added exactly as the gradients of
+        a one-rank call are, with the same per-tensor chunking, so the norm has the bits of the one-rank path on equal data.  Every rank
+        must pass the same set of names on the same micro-step: that cannot be checked locally and is not checked."""
+        scale = float(scale)
+        if not math.isfinite(scale):
+            raise ValueError(f"GradAccumulator.add: scale {scale} must be finite")
+        if clip_norm is not None and not float(clip_norm) > 0:
+            raise ValueError(f"GradAccumulator.add: clip_norm {clip_norm} must be positive (or None)")
+        max_norm = float(clip_norm) if clip_norm is not None else 0.0
+        entries, tab, grads = self._table(param_grads)
+        if not entries:
+            return
+        if group is None:
+            self._launch(tab, scale, max_norm)
+        else:
+            world = self._world(group)
+            if self.stage is None:
+                self.stage = self._alloc("stage", (int(self._offsets[-1]),)).zero_()
+            given = frozenset(grads)
+            if not self._staged <= given:        # slices no longer rewritten would be summed again and again: keep them 0
+                self.stage.zero_()
+            self._staged = given
+            has = [k for k, i in enumerate(entries) if i in grads]
+            if has:
+                first = tab[has]
+                first["p"] = self.stage.data_ptr() + 4 * self._offsets[[entries[k] for k in has]]
+                first["flags"] = _lib.GPC_FLAG_OVERWRITE
+                self._launch(first, scale / world, 0.0)
+            self._all_reduce(group)
+            tab["g"] = [self.stage.data_ptr() + 4 * int(self._offsets[i]) if i in grads else 0 for i in entries]
+            self._launch(tab, 1.0, max_norm)
+        self._live.update(grads)
+
+
+def rank_accum_selfcheck(rank, world, port, queue, backend, params, grads_per_micro_step, accumulate, clip_norm, lr, device_index=0):
+    """Entry point of ONE rank process of the accumulation self-check (tests/test_grad_accum_gpu.py starts `world` of them from a fork
+    server that never touched the GPU): a module whose parameters are the float32 arrays `params` ({name: array}), a Ranger and a
+    GradAccumulator over it, and the reference's loop over grads_per_micro_step (a list of {name: array}, this rank's gradients): every
+    micro-step i adds with scale 1 / accumulate, clip_norm and the process group, and steps and zeroes when i % accumulate == 0.
+    Puts (rank, "ok", {name: parameter}, {name: exp_avg}, (norm, coef) of the last add) on the queue as numpy arrays, or
+    (rank, "error: ...", None, None, None).  backend "gloo" lets the ranks share one GPU; "nccl" = RCCL, one rank per GPU, or world == 1
+    on a one-rank communicator; None: no process group at all (the one-rank path)."""
+    import os
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
+                      LOCAL_RANK=str(device_index if backend == "nccl" else rank))
+    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")        # as runner.rank_selfcheck: this RCCL needs dmabuf IPC
+    try:
+        import torch.distributed as dist
+        from . import dist as gd
+        group = None
+        if backend is not None:
+            gd.init_from_env(backend=backend, force=world == 1)
+            group = dist.group.WORLD
+        torch.cuda.set_device(device_index)
+        dev = torch.device("cuda", device_index)
+        net = torch.nn.Module()
+        for name, a in params.items():
+            net.register_parameter(name, torch.nn.Parameter(torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev), requires_grad=False))
+        opt = Ranger(net, lr=lr)
+        acc = GradAccumulator(opt)
+        for i, grads in enumerate(grads_per_micro_step):
+            g = {name: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev) for name, a in grads.items()}
+            acc.add(g, scale=1.0 / accumulate, clip_norm=clip_norm, group=group)
+            if i % accumulate == 0:
+                opt.step(acc.grads, clip_norm=None, lr=lr)
+                acc.zero()
+        torch.cuda.synchronize(dev)
+        out_p = {name: p.detach().cpu().numpy() for name, p in net.named_parameters()}
+        out_m = {name: opt._view("exp_avg", opt._index[name]).cpu().numpy() for name in out_p}
+        queue.put((rank, "ok", out_p, out_m, acc.scalars.cpu().numpy()))
+        if group is not None:
+            dist.barrier(device_ids=[device_index]) if backend == "nccl" else dist.barrier()
+            dist.destroy_process_group()
+    except Exception as e:   # the parent must never wait for a dead rank
+        import traceback
+        queue.put((rank, "error: " + repr(e) + "\n" + traceback.format_exc(), None, None, None))
 
 
 def flat_and_anneal_lr(it, total_iters, warmup_iters=0, warmup_factor=0.1, warmup_method="linear", anneal_point=0.72, anneal_method="cosine",

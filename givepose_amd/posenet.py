@@ -86,6 +86,24 @@ def _size_head_keyword(impl):
     return deco
 
 
+def _accumulator_keywords(impl):
+    """Decorator of `train_step`: the method also accepts the keyword-only options accumulator=, accumulate=, micro_step= and group=.
+    accumulator=None (the default): the decorated method itself runs, as it always did, and the other three must keep their defaults;
+    a GradAccumulator: `impl`, the accumulating form, runs with the same arguments.  The options are taken here and not in the `def`
+    line for the reason `_size_head_keyword` gives: inspect.signature() keeps showing the parameter list that callers and tests know,
+    which ends with size_head; the docstring names the options."""
+    def deco(fn):
+        @functools.wraps(fn)
+        def method(self, *args, accumulator=None, accumulate=1, micro_step=0, group=None, **kwargs):
+            if accumulator is None:
+                if group is not None or accumulate != 1 or micro_step != 0:
+                    raise ValueError(f"{fn.__name__}: group, accumulate and micro_step need accumulator=GradAccumulator(optimizer)")
+                return fn(self, *args, **kwargs)
+            return getattr(self, impl)(*args, **kwargs, accumulator=accumulator, accumulate=accumulate, micro_step=micro_step, group=group)
+        return method
+    return deco
+
+
 class PoseNet(nn.Module):
     def __init__(self, cfg: PoseNetConfig = PoseNetConfig(), dtype=torch.float16, use_graph=False, seed=None, inflight=1,
                  split_gemm=False, dcn_couple=None):
@@ -1391,6 +1409,7 @@ class PoseNet(nn.Module):
         return res
 
     # ------------------------------------------------------------------ one training step
+    @_accumulator_keywords("_train_step_accumulated")
     @torch.no_grad()
     def train_step(self, data, pose_loss, optimizer, device="cuda", groups=None, clip_norm=5.0, lr=None, size_head=None):
         """One iteration of the reference's loop (engine/train.py:113-129) for a single batch: `head_grads_backbone` (forward, the six
@@ -1406,8 +1425,21 @@ class PoseNet(nn.Module):
         running_var / num_batches_tracked are updated on the device as nn.BatchNorm1d(momentum=0.1) updates them
         (gps_bn_running_update), followed by `params_updated()`, so the next eval-mode forward folds the new statistics.  A fresh seed
         per step is the caller's business.
-        Not built: gradient accumulation over several batches (accumulate > 1; the reference clips on every micro-step and steps on the
-        last) and the all-reduce of the gradients across ranks."""
+        Keyword-only options accumulator=None, accumulate=1, micro_step=0, group=None (`_accumulator_keywords`).
+        accumulator=None (the default): the body above, one batch and one rank; accumulate, micro_step and group must keep their defaults.
+        accumulator=a givepose_amd.optim.GradAccumulator built over `optimizer`: the reference's loop with FLAGS.accumulate, to the
+        letter (engine/train.py:117-131) -- the gradients are added to the accumulator with scale 1 / accumulate and clip_grad_norm_ at
+        clip_norm is applied to the ACCUMULATED gradients, in place, on every micro-step (GradAccumulator.add), so a later micro-step
+        adds to an already clipped buffer; when micro_step % accumulate == 0 the optimiser steps from the accumulator without a second
+        clip and the accumulator is zeroed (res["stepped"] is True), otherwise no parameter moves and `params_updated()` is not called
+        (res["stepped"] is False).  The caller passes micro_step = global_step; as in the reference, whose global_step starts at 0, the
+        very first micro-step steps on one micro-batch.  res["param_grads"] stays unscaled.  With size_head= the running statistics
+        move on EVERY micro-step (the reference's BatchNorm is in train mode on every forward), followed by `params_updated()`.
+        group: a torch.distributed process group: the gradients are averaged over its ranks by one all_reduce of the accumulator's
+        staging buffer before they are added (DDP's average); every rank must call with the same names, i.e. the same size_head= choice.
+        With size_head= the three bn1 buffers are broadcast from rank 0 of the group after their update and before `params_updated()`
+        (DDP's broadcast_buffers), so that the replicas' eval-mode forwards stay the same.  The all-reduce starts after the whole backward
+        chain; there is no SyncBatchNorm: the batch statistics stay per rank and per micro-batch."""
         if getattr(optimizer, "model", None) is not self:
             raise ValueError("train_step: the optimizer must be a givepose_amd.optim.Ranger built over this model")
         if size_head is not None:
@@ -1420,4 +1452,36 @@ class PoseNet(nn.Module):
             size_grad.bn_running_update(sd["size_head.bn1.running_mean"], sd["size_head.bn1.running_var"],
                                         sd.get("size_head.bn1.num_batches_tracked"), stats["mean"], stats["var_unbiased"])
             self.params_updated()      # the step's own call came before the buffers moved
+        return res
+
+    @torch.no_grad()
+    def _train_step_accumulated(self, data, pose_loss, optimizer, device="cuda", groups=None, clip_norm=5.0, lr=None, size_head=None,
+                                accumulator=None, accumulate=1, micro_step=0, group=None):
+        """train_step with an accumulator: one micro-step of the reference's loop."""
+        if getattr(optimizer, "model", None) is not self:
+            raise ValueError("train_step: the optimizer must be a givepose_amd.optim.Ranger built over this model")
+        if size_head is not None:
+            self._size_head_mask(size_head, "train_step")
+        if getattr(accumulator, "optimizer", None) is not optimizer:
+            raise ValueError("train_step: the accumulator must be a givepose_amd.optim.GradAccumulator built over this optimizer")
+        if int(accumulate) != accumulate or accumulate < 1 or int(micro_step) != micro_step or micro_step < 0:
+            raise ValueError(f"train_step: accumulate {accumulate} must be a positive and micro_step {micro_step} a non-negative integer")
+        res = self.head_grads_backbone(data, pose_loss, device, groups=groups, **({} if size_head is None else {"size_head": size_head}))
+        accumulator.add(res["param_grads"], scale=1.0 / accumulate, clip_norm=clip_norm, group=group)
+        res["stepped"] = micro_step % accumulate == 0
+        if res["stepped"]:
+            optimizer.step(accumulator.grads, clip_norm=None, lr=lr)
+            accumulator.zero()
+        if size_head is not None:
+            from . import size_grad
+            sd, stats = self.state_dict(), res["size_head"]["stats"]
+            buffers = [sd["size_head.bn1.running_mean"], sd["size_head.bn1.running_var"], sd.get("size_head.bn1.num_batches_tracked")]
+            size_grad.bn_running_update(*buffers, stats["mean"], stats["var_unbiased"])
+            if group is not None:
+                import torch.distributed as dist
+                src = dist.get_global_rank(group, 0)
+                for b in buffers:
+                    if b is not None:
+                        dist.broadcast(b, src=src, group=group)
+            self.params_updated()
         return res
