@@ -45,8 +45,13 @@ Public surface mirrors the reference for this path:
                      step of Ranger (tools/torch_utils/solver/ranger2020.py: RAdam + Lookahead + gradient centralisation) over all
                      tensors in three launches, and the factor of the flat_and_anneal schedule
                      (tools/torch_utils/solver/lr_scheduler.py:177-263), on the device (optim.py, include/givepose_optim.h);
-                     train_step runs head_grads_backbone and then the step.  A device-side repack of the forward's weights is not
-                     part of this library
+                     train_step runs head_grads_backbone and then the step
+  PoseNet.set_repack("host" | "device"), PoseNet.repack_count, repack
+                     how the forward's packed weights follow the parameters.  "host" (the default): PoseNet._pack on the host, and
+                     params_updated() drops the packed weights and every plan.  "device": the same tensors are written in place on
+                     the device in at most four launches (permutations, concatenations, fp16 / split-plane roundings, the BatchNorm
+                     fold in fp32, the matrix folds in float64), so params_updated() costs no host copy, no synchronise and no graph
+                     recapture (repack.py, include/givepose_repack.h); for the configurations train_step accepts
   GradAccumulator, train_step(accumulator=, accumulate=, micro_step=, group=)
                      FLAGS.accumulate and the gradient all-reduce across ranks (engine/train.py:117-131): the micro-steps' gradients
                      added, scaled and clipped in place in one flat device buffer in three launches, exchanged between ranks by one
@@ -54,7 +59,7 @@ Public surface mirrors the reference for this path:
 """
 from .config import PoseNetConfig  # noqa: F401
 from .posenet import PoseNet  # noqa: F401
-from . import bb_grad, enc_grad, optim, pnp_grad, size_grad, xyz_grad  # noqa: F401  (ctypes wrappers only: the library is loaded at the first call)
+from . import bb_grad, enc_grad, optim, pnp_grad, repack, size_grad, xyz_grad  # noqa: F401  (ctypes wrappers only: the library is loaded at the first call)
 from .optim import GradAccumulator, Ranger, clip_grad_norm_, flat_and_anneal_lr  # noqa: F401
 
 

@@ -306,6 +306,39 @@ SIZEGRAD_PROTOTYPES = {
 }
 GPS_CHUNK, GPS_MAX_C, GPS_FORWARD_LAUNCHES, GPS_BACKWARD_LAUNCHES, GPS_DROP_THRESHOLD = 4, 4096, 3, 3, 858993459
 
+
+# the weight-repack family (include/givepose_repack.h, prefix gpr_; tests/test_repack_cpu.py checks both ways)
+class RepackEntry(Structure):         # gpr_entry: one strided fp32 view -> a dense run of a packed tensor
+    _fields_ = [("src", c_void_p), ("dst", c_void_p), ("src_numel", c_longlong), ("dst_numel", c_longlong), ("src_off", c_longlong),
+                ("dst_off", c_longlong), ("plane_stride", c_longlong), ("strides", c_longlong * 4), ("dims", c_int * 4), ("kind", c_int),
+                ("pad", c_int)]
+
+
+class RepackBnFold(Structure):        # gpr_bnfold
+    _fields_ = [(n, c_void_p) for n in ("w", "b", "bn_w", "bn_b", "mean", "var", "w_out", "b_out")] + [
+        ("w_numel", c_longlong), ("c_numel", c_longlong), ("C", c_int), ("K", c_int), ("eps", c_float), ("pad", c_int)]
+
+
+class RepackMatFold(Structure):       # gpr_matfold
+    _fields_ = [(n, c_void_p) for n in ("A", "B", "add", "out32", "out64")] + [
+        (n, c_longlong) for n in ("a_numel", "b_numel", "add_numel", "out32_numel", "out64_numel")] + [
+        (n, c_int) for n in ("M", "N", "K", "a_rs", "b_rs", "ld32", "ld64", "b_f64", "level", "pad")]
+
+
+class RepackInfo(Structure):          # gpr_info
+    _fields_ = [(n, c_longlong) for n in ("bytes", "off_chunks", "off_bn", "off_mat", "off_mchunks")] + [
+        (n, c_int) for n in ("n_entries", "n_chunks", "n_bn", "n_bn_blocks", "n_mat", "n_mchunks0", "n_mchunks1", "pad")]
+
+
+REPACK_PROTOTYPES = {
+    "gpr_tables_bytes": ([POINTER(RepackEntry), c_int, POINTER(RepackBnFold), c_int, POINTER(RepackMatFold), c_int], c_longlong),
+    "gpr_tables_upload": ([POINTER(RepackEntry), c_int, POINTER(RepackBnFold), c_int, POINTER(RepackMatFold), c_int, _P, _P, c_longlong,
+                           POINTER(RepackInfo), _P], c_int),
+    "gpr_repack": ([_P, POINTER(RepackInfo), _P], c_int),
+}
+GPR_CHUNK, GPR_REPACK_LAUNCHES, GPR_REPACK_LAUNCHES_F32, GPR_MAX_ENTRIES, GPR_MAX_DIMS = 4096, 4, 3, 65536, 4
+GPR_KIND_F32, GPR_KIND_F16, GPR_KIND_SPLIT = 0, 1, 2
+
 _lib = None
 
 
@@ -327,7 +360,8 @@ def load():
                                       + list(GRAD_PROTOTYPES.items()) + list(HEADGRAD_PROTOTYPES.items())
                                       + list(XYZGRAD_PROTOTYPES.items()) + list(ENCGRAD_PROTOTYPES.items())
                                       + list(BBGRAD_PROTOTYPES.items()) + list(OPTIM_PROTOTYPES.items())
-                                      + list(SIZEGRAD_PROTOTYPES.items()) + list(ACCUM_PROTOTYPES.items())):
+                                      + list(SIZEGRAD_PROTOTYPES.items()) + list(ACCUM_PROTOTYPES.items())
+                                      + list(REPACK_PROTOTYPES.items())):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.argtypes = argtypes
         fn.restype = restype

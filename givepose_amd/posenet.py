@@ -177,6 +177,7 @@ class PoseNet(nn.Module):
                     lib.gp_graph_destroy(plan["graph"])
                     plan["graph"] = None
         self._packed = None
+        self._repacker = None
         self._pnp_f32 = None
         self._xyz_f32 = {}
         self._enc_f32 = {}
@@ -190,8 +191,53 @@ class PoseNet(nn.Module):
         The plans go too (`_reset_plans`): a plan is not only activation buffers -- its captured hipGraph holds raw pointers to the
         packed weight tensors that are dropped here, and its buffers hold weight-derived rows (the position embeddings of the 'att'
         heads, a_pos / p_pos, are copied from `_packed` when the plan is built).  The next forward rebuilds its plan, as after
-        load_state_dict."""
+        load_state_dict.
+        Under set_repack("device") with packed weights present, none of that is dropped but the backward's caches: the current stream is made
+        to wait for every slot stream (a forward issued with wait=False may still read the weights), then the packed tensors are rewritten
+        in place from the parameters by gpr_repack on the current stream (givepose_amd/repack.py: no host copy, no device synchronise).
+        Every packed tensor keeps its address, so the plans and their captured graphs stay valid, and forward_device makes its slot stream
+        wait for the current one, which orders the next forward behind the repack."""
+        if self._repack_mode == "device" and self._packed is not None and self._repacker is not None:
+            cur = torch.cuda.current_stream(self._repacker.device)
+            for s in self._streams.values():
+                cur.wait_stream(s)
+            self._repacker.run(self._repacker.sources_of(self))
+            self.repack_count += 1
+            self._pnp_f32 = None
+            self._xyz_f32 = {}
+            self._enc_f32 = {}
+            return
         self._reset_plans()
+
+    # how `_packed` is made and refreshed: "host" (`_pack`: host folds and roundings, plans rebuilt after every change) or "device"
+    _repack_mode = "host"
+    _repacker = None          # repack.DeviceRepack of the current `_packed` ("device" mode)
+    repack_count = 0          # device repacks run so far (the first pack included)
+
+    def set_repack(self, mode):
+        """"host" (the default): `_pack` builds the packed weights on the host and `params_updated()` drops them with every plan.
+        "device": the packed weights are built and refreshed on the device by the gpr_ family; the configuration is checked here
+        (NotImplementedError names what the device repack does not serve: the resnet34 backbone, the 'att' encoder and head, use_dcn='',
+        defer_ln=True).  Switching drops the packed weights and the plans, as load_state_dict does."""
+        if mode not in ("host", "device"):
+            raise ValueError(f"set_repack: {mode!r}, expected 'host' or 'device'")
+        if mode == "device":
+            from . import repack
+            repack.plan(self.cfg, self.compute_dtype, self.split_gemm)
+        if mode != self._repack_mode:
+            self._reset_plans()
+            self._repack_mode = mode
+        return self
+
+    def _pack_device(self, device):
+        """`_pack` under set_repack("device"): allocates the packed tensors (the keys, shapes and dtypes of `_pack`) and fills them on the
+        device.  The parameters must be contiguous float32 on `device` (ValueError names the first that is not)."""
+        from . import repack
+        rp = repack.DeviceRepack(repack.plan(self.cfg, self.compute_dtype, self.split_gemm), device)
+        rp.run(rp.sources_of(self))
+        self.repack_count += 1
+        self._repacker, self._packed = rp, rp.packed
+        return self._packed
 
     def __del__(self):
         try:
@@ -213,7 +259,10 @@ class PoseNet(nn.Module):
     def _pack(self, device):
         """Reference-layout fp32 state dict -> kernel-layout device tensors (done once).  Every fold (eval BatchNorm into
         a conv, conv1x1 into input_proj, LayerNorm affine into fc1) and every rounding to the storage type happens on the
-        HOST; the device only ever runs this library's kernels (the one device-side step is gp_convnext_mlp_pack_w2)."""
+        HOST; the device only ever runs this library's kernels (the one device-side step is gp_convnext_mlp_pack_w2).
+        Under set_repack("device") the same tensors are made on the device instead (`_pack_device`)."""
+        if self._repack_mode == "device":
+            return self._pack_device(device)
         sd = {k: v.detach().to(device="cpu", dtype=torch.float32) if v.is_floating_point() else v.detach().cpu()
               for k, v in self.state_dict().items()}
         T = self.compute_dtype
