@@ -29,7 +29,8 @@ stride 2: 8 x 4 outputs, grid.x 4; every other map is non-square):
                                                  out-of-range tap are finite and within bound, outputs that sample it are not finite
 
 Not covered: the measurement arm GP_DCN_FOLD=1 (another association by design); the A/B switches GP_DCN_PATCH and GP_DCN_XCD, which are read
-once per process; GP_DCN_LDS_PAD.  The backward: tests/test_hip_dcnv3_any.py.
+once per process; GP_DCN_LDS_PAD.  The backward, per element in the same way: tests/dcnv3_backward_reference.py and
+tests/test_dcnv3_backward_conformance_gpu.py (goldens and the reference test's channel counts: tests/test_hip_dcnv3_any.py).
 """
 import ctypes
 import os

@@ -6,6 +6,8 @@ Everything else (depth-wise + LayerNorm + GELU, the DCNv3 core, GroupNorm + ReLU
 max|got - ref| / max|ref| at most 8 times the CPU float32 figure of the same inputs (never less than 2^-24, one rounding of the
 largest element); both figures are printed.  The encoder's float64 reference is the restatement evaluated at the DEVICE's gates (ReLU
 masks and sampling cells read back from what the device saved), which may differ from float64's only inside the margin set.
+The DCNv3 core once more PER ELEMENT, on odd non-square maps with taps exactly on the sampling edges, against tests/dcnv3_reference.py and
+tests/dcnv3_backward_reference.py (test_dcnv3_core_per_element_at_the_sampling_edges; its ratio lines: profiles/dcnv3_backward_conformance.txt).
 
 Measured on an MI355X (the ratio lines of that run are kept in profiles/enc_backward.txt):
 
@@ -27,6 +29,8 @@ import numpy as np
 import pytest
 import torch
 
+import dcnv3_backward_reference as DB
+import dcnv3_reference as DR
 import enc_backward_cases as C
 import enc_backward_ref as R
 from test_xyz_backward_gpu import Guarded, bits, chain_bound, d64, normal, rng, same_bits, within
@@ -178,6 +182,60 @@ def test_dcnv3_core_equal_logits_equal_gm():
     dl = bw["dmask_logits"].cpu().double()[row].reshape(4, 9)
     assert torch.allclose(fw["mask"].cpu()[row], torch.full((36,), 1 / 9), rtol=0, atol=2 * U)
     assert torch.all(dl.abs() <= 16 * U * gm.abs()[:, None] / 9 + 64 * U * 0.75 * d64(dy)[row].abs().reshape(4, 64).sum(1)[:, None] / 9), dl
+
+
+CORE_EDGE_CASES = [
+    DR.mk("core-edges-N2-5x8", torch.float32, N=2, H=5, W=8, s=2, iset="edges", logits=True),      # 3 x 4 outputs, 864 taps: every pair of the edge tables
+    DR.mk("core-c3-N1-7x4", torch.float32, N=1, H=7, W=4, s=2, logits=True),
+]
+
+
+@pytest.mark.parametrize("case", CORE_EDGE_CASES, ids=lambda c: c.name)
+def test_dcnv3_core_per_element_at_the_sampling_edges(case):
+    """gpe_dcnv3_core_forward / _backward on odd, non-square maps with taps exactly on the sampling edges, per element: y against
+    dcnv3_reference.ref (the logits case); dxp and doffset against the bounds of dcnv3_backward_reference (the general backward at G 4,
+    D 64, K 3, stride 2, pad 1, os 1, float32) evaluated on the mask the DEVICE saved; dmask_logits = m (gm - sum m gm) against the float64
+    value on the same mask, its bound being grad_mask's pushed through the expression (dcnv3_backward_reference.dlogits_ref, derived in
+    that module's docstring).  A bound of 0 -- every doffset slot of a tap outside the map, every dxp element nothing reaches, every y whose
+    taps are all outside -- asks for an exact zero.  doffset and dmask_logits have one writer per element: equal bits on a second launch."""
+    from givepose_amd import enc_grad
+    c = case
+    I = DR.inputs(c)
+    rows = DR.n_rows(c)
+    assert rows == R.core_rows(c.N, c.H, c.W) and (c.G, c.D, c.kh, c.kw, c.sh, c.ph, c.os, c.rc) == (4, 64, 3, 3, 2, 1, 1.0, 0)
+    if c.iset == "edges":
+        assert all(n > 0 for n in DR.classify(c, I).values())
+    dy = DB.grad_output(c)
+    xp, off, logits, dyd = I["x"].cuda(), I["off"].view(rows, 72).cuda(), I["mask"].view(rows, 36).cuda(), dy.cuda()
+    guard = Guarded()
+    fw = enc_grad.dcnv3_core_forward(xp, off, logits, alloc=guard)
+    bw = enc_grad.dcnv3_core_backward(xp, off, fw["mask"], dyd, alloc=guard)
+    again = enc_grad.dcnv3_core_backward(xp, off, fw["mask"], dyd, alloc=guard)
+    guard.check()
+    failures = []
+
+    def hold(got, v, bound, what):
+        zeros = what in ("dxp", "doffset") or (what == "y" and c.iset == "edges")      # the case must hold exact zeros there
+        assert bool((bound > 0).any()) and (bool((bound == 0).any()) or not zeros), what
+        ratio, msg = DR.check(got, v, bound, f"{c.name} {what}")
+        print(f"GPU_RATIO {c.name} {what} {ratio:.4f}")
+        if msg is not None:
+            failures.append(msg)
+
+    hold(fw["y"], *DR.ref(I, c), "y")
+    saved = fw["mask"].cpu()
+    cb = c._replace(logits=False, entry="any")
+    r = DB.ref(dict(x=I["x"], off=I["off"], mask=saved.reshape(-1), gout=dy), cb)
+    hold(bw["dxp"], *r["grad_input"], "dxp")
+    hold(bw["doffset"], *r["grad_offset"], "doffset")
+    hold(bw["dmask_logits"], *DB.dlogits_ref(saved.view(rows, 4, 9), *r["grad_mask"], 9), "dmask_logits")
+    lh, lw, _ = DR.locations(c, I, torch.float32)
+    outside = ~((lh > -1) & (lw > -1) & (lh < c.H) & (lw < c.W))
+    assert bool(outside.any()) and bool((r["grad_offset"][1][outside] == 0).all())
+    for k in ("doffset", "dmask_logits"):
+        if not torch.equal(bits(bw[k]), bits(again[k])):
+            failures.append(f"{c.name} {k}: a second launch gives other bits")
+    assert not failures, "\n".join(failures)
 
 
 # ------------------------------------------------------------------------------------------------ GroupNorm + ReLU

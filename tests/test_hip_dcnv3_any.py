@@ -7,7 +7,9 @@ double / float / half, per-axis geometry, any group_channels, and the BACKWARD -
 Tolerances: fp64 1e-6 relative-to-scale (dcnv3_core_pytorch builds its sampling grid from fp32 linspace), fp32 the
 reference test's own rtol 1e-2 / atol 1e-3 (test.py:88, 136) tightened to 1e-4 relative-to-scale, fp16 3e-3.
 The forward per element against a float64 reference with a derived bound (non-square maps, taps on the sampling edges, more than 64
-taps, non-finite pixels): tests/test_dcnv3_conformance_gpu.py.
+taps, non-finite pixels): tests/test_dcnv3_conformance_gpu.py.  The backward per element in the same way (taps on the sampling edges, buffer
+guards, one writer per grad_offset / grad_mask element, more than 64 taps, remove_center with per-axis geometry):
+tests/dcnv3_backward_reference.py and tests/test_dcnv3_backward_conformance_gpu.py.
 """
 import numpy as np
 import pytest
