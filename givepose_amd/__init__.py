@@ -56,6 +56,11 @@ Public surface mirrors the reference for this path:
                      FLAGS.accumulate and the gradient all-reduce across ranks (engine/train.py:117-131): the micro-steps' gradients
                      added, scaled and clipped in place in one flat device buffer in three launches, exchanged between ranks by one
                      all_reduce, and stepped from by Ranger (optim.py, include/givepose_accum.h)
+  TrainBatchBuilder, fs_net_scale, sym_info
+                     the training batch of datasets/load_data_nocs.py:180-386 from uint8 frames and labels: the DZI-augmented crops
+                     (tools/dataset_utils.py:32-82), the NOCS / IVFC coordinate targets and their masks, and defor_2D
+                     (datasets/data_augmentation.py:11-33) with explicit or seeded draws, in two launches on the device
+                     (train_batch.py, include/givepose_traindata.h)
 """
 from .config import PoseNetConfig  # noqa: F401
 from .posenet import PoseNet  # noqa: F401
@@ -90,4 +95,7 @@ def __getattr__(name):
     if name in ("PoseLoss", "LossConfig", "LossAccumulator", "pose_decode_train", "pose_decode_train_backward"):   # losses/pose_loss.py:13
         from . import loss
         return getattr(loss, name)
+    if name in ("TrainBatchBuilder", "fs_net_scale", "sym_info"):                # datasets/load_data_nocs.py:180
+        from . import train_batch
+        return getattr(train_batch, name)
     raise AttributeError(name)

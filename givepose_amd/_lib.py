@@ -339,6 +339,13 @@ REPACK_PROTOTYPES = {
 GPR_CHUNK, GPR_REPACK_LAUNCHES, GPR_REPACK_LAUNCHES_F32, GPR_MAX_ENTRIES, GPR_MAX_DIMS = 4096, 4, 3, 65536, 4
 GPR_KIND_F32, GPR_KIND_F16, GPR_KIND_SPLIT = 0, 1, 2
 
+# the training-batch family (include/givepose_traindata.h, prefix gpt_; tests/test_train_batch_cpu.py checks both ways)
+TRAINDATA_PROTOTYPES = {
+    "gpt_crop_train": ([_P] * 21 + [c_int] * 7 + [_P], c_int),
+    "gpt_mask_deform": ([_P] * 3 + [c_ulonglong, _P, c_int, c_int, _P], c_int),
+}
+GPT_MAX_PIXELS, GPT_TRAIN_BATCH_LAUNCHES = 65536, 2
+
 _lib = None
 
 
@@ -361,7 +368,7 @@ def load():
                                       + list(XYZGRAD_PROTOTYPES.items()) + list(ENCGRAD_PROTOTYPES.items())
                                       + list(BBGRAD_PROTOTYPES.items()) + list(OPTIM_PROTOTYPES.items())
                                       + list(SIZEGRAD_PROTOTYPES.items()) + list(ACCUM_PROTOTYPES.items())
-                                      + list(REPACK_PROTOTYPES.items())):
+                                      + list(REPACK_PROTOTYPES.items()) + list(TRAINDATA_PROTOTYPES.items())):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.argtypes = argtypes
         fn.restype = restype

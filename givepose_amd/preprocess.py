@@ -91,12 +91,22 @@ def crop_params(bboxes, im_H, im_W, img_size=256, out_res=64, pad_scale=1.5):
         raise ValueError(f"crop_params: degenerate detection box(es) at index {bad.tolist()}: (y1,x1,y2,x2) = {bboxes[bad].tolist()}")
     cx, cy = 0.5 * (x1 + x2), 0.5 * (y1 + y2)
     scale = np.minimum(ext * pad_scale, max(im_H, im_W)) * 1.0
+    wh = np.stack([np.minimum(im_W, x2) - np.maximum(0, x1), np.minimum(im_H, y2) - np.maximum(0, y1)], 1).astype(np.float32)
+    P = crop_params_from_center_scale(cx, cy, scale, img_size, out_res)
+    return {"inv_img": P["inv_img"], "inv_out": P["inv_out"], "roi_wh": wh, "bbox_center": P["bbox_center"], "resize_ratio": P["resize_ratio"]}
+
+
+def crop_params_from_center_scale(cx, cy, scale, img_size=256, out_res=64):
+    """The crop of a given centre and side (n,) each, float64 -- crop_params after its box arithmetic, for callers that choose the
+    square themselves (train_batch.py: the DZI-augmented box) -> inv_img, inv_out (float64), bbox_center, resize_ratio (float32)."""
+    cx, cy, scale = (np.asarray(v, dtype=np.float64).reshape(-1) for v in (cx, cy, scale))
+    if not (np.all(np.isfinite(cx)) and np.all(np.isfinite(cy)) and np.all(np.isfinite(scale)) and np.all(scale > 0)):
+        raise ValueError("crop_params_from_center_scale: centre and scale must be finite and the scale positive")
     inv_img = _invert_batch(_affine_dst_from_src_batch(cx, cy, scale, float(img_size)))
     inv_out = _invert_batch(_affine_dst_from_src_batch(cx, cy, scale, float(out_res)))
-    wh = np.stack([np.minimum(im_W, x2) - np.maximum(0, x1), np.minimum(im_H, y2) - np.maximum(0, y1)], 1).astype(np.float32)
     ctr = np.stack([cx, cy], 1).astype(np.float32)
     ratio = (out_res / scale).astype(np.float32)
-    return {"inv_img": inv_img, "inv_out": inv_out, "roi_wh": wh, "bbox_center": ctr, "resize_ratio": ratio}
+    return {"inv_img": inv_img, "inv_out": inv_out, "bbox_center": ctr, "resize_ratio": ratio}
 
 
 def crop_params_loop(bboxes, im_H, im_W, img_size=256, out_res=64, pad_scale=1.5):
