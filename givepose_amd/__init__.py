@@ -52,6 +52,11 @@ Public surface mirrors the reference for this path:
                      the device in at most four launches (permutations, concatenations, fp16 / split-plane roundings, the BatchNorm
                      fold in fp32, the matrix folds in float64), so params_updated() costs no host copy, no synchronise and no graph
                      recapture (repack.py, include/givepose_repack.h); for the configurations train_step accepts
+  PoseNet.set_backward_precision("fp32" | "bf16"), PoseNet.backward_precision, bb_grad.matmul_bf16, precision= of bb_grad's block and backbone calls
+                     the backbone's recompute and backward in mixed precision: under "bf16" the six dense contractions of every
+                     ConvNeXt block multiply bf16-rounded operands on v_mfma_f32_32x32x16_bf16 and add in fp32, everything else
+                     stays the fp32 code; "fp32" (the default) is bit for bit what it was (csrc/grad_gemm_bf16.hpp,
+                     include/givepose_bbgrad_bf16.h)
   GradAccumulator, train_step(accumulator=, accumulate=, micro_step=, group=)
                      FLAGS.accumulate and the gradient all-reduce across ranks (engine/train.py:117-131): the micro-steps' gradients
                      added, scaled and clipped in place in one flat device buffer in three launches, exchanged between ranks by one

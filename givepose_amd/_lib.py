@@ -258,6 +258,21 @@ BBGRAD_PROTOTYPES = {
 }
 GPB_MAX_STAGES, GPB_STEM_PATCH, GPB_DOWN_PATCH = 8, 4, 2
 
+# its mixed-precision forms (include/givepose_bbgrad_bf16.h, prefix gpbm_; tests/test_bb_bf16_cpu.py checks both ways): a trailing
+# `precision` on the block and backbone entry points and their size queries, and the bf16 contraction as a piece of its own
+GPB_PREC_F32, GPB_PREC_BF16 = 0, 1
+BBGRAD_BF16_PROTOTYPES = {
+    "gpbm_matmul_bf16_workspace": ([c_int] * 3, c_longlong),
+    "gpbm_matmul_bf16": ([_P, _P] + [c_int] * 5 + [_P, _P, c_longlong, _P], c_int),
+    "gpbm_block_workspace": ([c_int] * 5, c_longlong),
+    "gpbm_block_forward_save": (BBGRAD_PROTOTYPES["gpb_block_forward_save"][0] + [c_int], c_int),
+    "gpbm_block_backward": (BBGRAD_PROTOTYPES["gpb_block_backward"][0] + [c_int], c_int),
+    "gpbm_backbone_forward_workspace": (BBGRAD_PROTOTYPES["gpb_backbone_forward_workspace"][0] + [c_int], c_longlong),
+    "gpbm_backbone_forward_save": (BBGRAD_PROTOTYPES["gpb_backbone_forward_save"][0] + [c_int], c_int),
+    "gpbm_backbone_backward_workspace": (BBGRAD_PROTOTYPES["gpb_backbone_backward_workspace"][0] + [c_int], c_longlong),
+    "gpbm_backbone_backward": (BBGRAD_PROTOTYPES["gpb_backbone_backward"][0] + [c_int], c_int),
+}
+
 
 # the optimiser family (include/givepose_optim.h, prefix gpo_; tests/test_optim_cpu.py checks both ways)
 class OptTensor(Structure):           # gpo_tensor: one parameter of a step (device pointers, host table)
@@ -366,7 +381,7 @@ def load():
     for name, (argtypes, restype) in (list(PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items())
                                       + list(GRAD_PROTOTYPES.items()) + list(HEADGRAD_PROTOTYPES.items())
                                       + list(XYZGRAD_PROTOTYPES.items()) + list(ENCGRAD_PROTOTYPES.items())
-                                      + list(BBGRAD_PROTOTYPES.items()) + list(OPTIM_PROTOTYPES.items())
+                                      + list(BBGRAD_PROTOTYPES.items()) + list(BBGRAD_BF16_PROTOTYPES.items()) + list(OPTIM_PROTOTYPES.items())
                                       + list(SIZEGRAD_PROTOTYPES.items()) + list(ACCUM_PROTOTYPES.items())
                                       + list(REPACK_PROTOTYPES.items()) + list(TRAINDATA_PROTOTYPES.items())):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing

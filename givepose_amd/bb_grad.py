@@ -139,6 +139,28 @@ def _ints(v):
     return (ctypes.c_int * len(v))(*v)
 
 
+PRECISIONS = {"fp32": _lib.GPB_PREC_F32, "bf16": _lib.GPB_PREC_BF16}
+
+
+def _prec(precision):
+    """The GPB_PREC_* value of "fp32" or "bf16" (include/givepose_bbgrad_bf16.h)."""
+    if not isinstance(precision, str) or precision not in PRECISIONS:
+        raise ValueError(f"precision: {precision!r}, expected 'fp32' or 'bf16'")
+    return PRECISIONS[precision]
+
+
+def _entry(L, stem, prec):
+    """(function, its name, trailing arguments) of gpb_<stem> in a precision: "fp32" is the gpb_ entry point itself."""
+    if prec == _lib.GPB_PREC_F32:
+        return getattr(L, "gpb_" + stem), "gpb_" + stem, ()
+    return getattr(L, "gpbm_" + stem), "gpbm_" + stem, (prec,)
+
+
+def _query(L, stem, prec, *args):
+    fn, _, tail = _entry(L, stem, prec)
+    return fn(*args, *tail)
+
+
 def _block_struct(tensors, C, dev, what):
     st = _lib.BbBlockParams()
     for f, (k, s) in zip(_lib.BbBlockParams.FIELDS, block_shapes(C).items()):
@@ -256,9 +278,12 @@ def patch_conv_backward(dy, x, w, nchw, alloc=None):
 
 
 @torch.no_grad()
-def block_forward_save(x, params, alloc=None):
+def block_forward_save(x, params, alloc=None, precision="fp32"):
     """One ConvNeXt block on x (N,H,W,C): params {name over BLOCK_KEYS: tensor}
-    -> {"dwout": (rows,C), "mean", "rstd": (rows,), "h": (rows,4C), "y2": (rows,C), "out": (N,H,W,C)}, rows = N H W."""
+    -> {"dwout": (rows,C), "mean", "rstd": (rows,), "h": (rows,4C), "y2": (rows,C), "out": (N,H,W,C)}, rows = N H W.
+    precision="bf16": fc1 and fc2 multiply bf16-rounded operands and add in fp32 (gpbm_block_forward_save); everything else, and
+    every shape and dtype, is as in "fp32", which is gpb_block_forward_save bit for bit."""
+    prec = _prec(precision)
     dev = _dev(x)
     if x.dim() != 4:
         raise ValueError(f"x: {tuple(x.shape)}, expected (N,H,W,C)")
@@ -271,17 +296,21 @@ def block_forward_save(x, params, alloc=None):
     out = {"dwout": alloc("dwout", (rows, C)), "mean": alloc("mean", (rows,)), "rstd": alloc("rstd", (rows,)), "h": alloc("h", (rows, 4 * C)),
            "y2": alloc("y2", (rows, C)), "out": alloc("out", (N, H, W, C))}
     L = _lib.load()
-    nbytes = L.gpb_block_workspace(N, H, W, C)
+    nbytes = _query(L, "block_workspace", prec, N, H, W, C)
     ws = _ws(alloc, nbytes)
-    _call(dev, L.gpb_block_forward_save, "gpb_block_forward_save", x.data_ptr(), ctypes.byref(st), N, H, W, C,
-          *(out[k].data_ptr() for k in ("dwout", "mean", "rstd", "h", "y2", "out")), ws.data_ptr(), nbytes, _stream(dev))
+    fn, name, tail = _entry(L, "block_forward_save", prec)
+    _call(dev, fn, name, x.data_ptr(), ctypes.byref(st), N, H, W, C,
+          *(out[k].data_ptr() for k in ("dwout", "mean", "rstd", "h", "y2", "out")), ws.data_ptr(), nbytes, _stream(dev), *tail)
     return out
 
 
 @torch.no_grad()
-def block_backward(g, x, params, saved, alloc=None):
+def block_backward(g, x, params, saved, alloc=None, precision="fp32"):
     """Backward of block_forward_save from g = d out (N,H,W,C) and what the forward saved
-    -> {"dx": (N,H,W,C)} and the nine parameter gradients under BLOCK_KEYS."""
+    -> {"dx": (N,H,W,C)} and the nine parameter gradients under BLOCK_KEYS.
+    precision="bf16": the four contractions (d W2, d h, d W1, fc1's dX) multiply bf16-rounded operands and add in fp32; `saved` may
+    come from a forward of either precision."""
+    prec = _prec(precision)
     dev = _dev(g)
     if x.dim() != 4:
         raise ValueError(f"x: {tuple(x.shape)}, expected (N,H,W,C)")
@@ -296,12 +325,36 @@ def block_backward(g, x, params, saved, alloc=None):
     out = {"dx": alloc("dx", (N, H, W, C)), **{k: alloc(k, s) for k, s in block_shapes(C).items()}}
     gs = _block_struct(out, C, dev, "grads")
     L = _lib.load()
-    nbytes = L.gpb_block_workspace(N, H, W, C)
+    nbytes = _query(L, "block_workspace", prec, N, H, W, C)
     ws = _ws(alloc, nbytes)
-    _call(dev, L.gpb_block_backward, "gpb_block_backward", g.data_ptr(), x.data_ptr(), ctypes.byref(st),
+    fn, name, tail = _entry(L, "block_backward", prec)
+    _call(dev, fn, name, g.data_ptr(), x.data_ptr(), ctypes.byref(st),
           *(saved[k].data_ptr() for k in ("dwout", "mean", "rstd", "h", "y2")), N, H, W, C, ctypes.byref(gs), out["dx"].data_ptr(), ws.data_ptr(),
-          nbytes, _stream(dev))
+          nbytes, _stream(dev), *tail)
     return out
+
+
+@torch.no_grad()
+def matmul_bf16(a, b, trans_a=False, trans_b=False, alloc=None):
+    """The bf16 contraction of the "bf16" precision as a piece of its own (gpbm_matmul_bf16): C (M,N) fp32 = op(a) op(b) with every
+    element of a and b rounded to bf16 (nearest even) and the products added in fp32.  a is (M,K), or (K,M) with trans_a; b is (K,N),
+    or (N,K) with trans_b; both contiguous float32 on the device.  No atomic: equal inputs give equal bits."""
+    dev = _dev(a)
+    if not torch.is_tensor(b) or a.dim() != 2 or b.dim() != 2:
+        raise ValueError("a and b must be matrices")
+    (K, M) = a.shape if trans_a else a.shape[::-1]
+    (N, Kb) = b.shape if trans_b else b.shape[::-1]
+    if K != Kb or min(M, N, K) < 1:
+        raise ValueError(f"a {tuple(a.shape)} (trans_a={bool(trans_a)}) and b {tuple(b.shape)} (trans_b={bool(trans_b)}) do not contract")
+    _chk(a, dev, a.shape, "a"), _chk(b, dev, b.shape, "b")
+    alloc = alloc or _default_alloc(dev)
+    c = alloc("c", (M, N))
+    L = _lib.load()
+    nbytes = L.gpbm_matmul_bf16_workspace(M, N, K)
+    ws = _ws(alloc, nbytes)
+    _call(dev, L.gpbm_matmul_bf16, "gpbm_matmul_bf16", a.data_ptr(), b.data_ptr(), M, N, K, int(bool(trans_a)), int(bool(trans_b)), c.data_ptr(),
+          ws.data_ptr(), nbytes, _stream(dev))
+    return c
 
 
 # ------------------------------------------------------------------------------------------------ the backbone
@@ -313,9 +366,12 @@ def _check_img(img, dev, n):
 
 
 @torch.no_grad()
-def backbone_forward_save(img, params, cfg, alloc=None):
+def backbone_forward_save(img, params, cfg, alloc=None, precision="fp32"):
     """The ConvNeXt backbone in fp32 (gpb_backbone_forward_save): img (B,3,S,S), params {name: fp32 device tensor} over PARAM_KEYS(cfg)
-    -> (saved {name: tensor} over saved_shapes(cfg, B, S), feat (B,C_last,S/32,S/32) NCHW for four stages)."""
+    -> (saved {name: tensor} over saved_shapes(cfg, B, S), feat (B,C_last,S/32,S/32) NCHW for four stages).
+    precision="bf16": fc1 and fc2 of every block multiply bf16-rounded operands and add in fp32 (gpbm_backbone_forward_save); the
+    saved table has the same shapes and dtypes."""
+    prec = _prec(precision)
     dev = _dev(img)
     dims, depths = _dd(cfg)
     n = len(dims)
@@ -328,17 +384,21 @@ def backbone_forward_save(img, params, cfg, alloc=None):
     last = S // (4 << (n - 1))
     feat = alloc("feat", (B, dims[-1], last, last))
     L = _lib.load()
-    nbytes = L.gpb_backbone_forward_workspace(_ints(dims), _ints(depths), n, B, S)
+    nbytes = _query(L, "backbone_forward_workspace", prec, _ints(dims), _ints(depths), n, B, S)
     ws = _ws(alloc, nbytes)
-    _call(dev, L.gpb_backbone_forward_save, "gpb_backbone_forward_save", img.data_ptr(), pt, _ints(dims), _ints(depths), n, B, S, vt,
-          feat.data_ptr(), ws.data_ptr(), nbytes, _stream(dev))
+    fn, name, tail = _entry(L, "backbone_forward_save", prec)
+    _call(dev, fn, name, img.data_ptr(), pt, _ints(dims), _ints(depths), n, B, S, vt,
+          feat.data_ptr(), ws.data_ptr(), nbytes, _stream(dev), *tail)
     return saved, feat
 
 
 @torch.no_grad()
-def backbone_backward(params, saved, img, g_feat, cfg, alloc=None):
+def backbone_backward(params, saved, img, g_feat, cfg, alloc=None, precision="fp32"):
     """gpb_backbone_backward: from g_feat (like feat), img and what backbone_forward_save returned for it (and the same params)
-    -> ({name: gradient} over PARAM_KEYS(cfg), each in its parameter's shape, d img (B,3,S,S))."""
+    -> ({name: gradient} over PARAM_KEYS(cfg), each in its parameter's shape, d img (B,3,S,S)).
+    precision="bf16": the four backward contractions of every block multiply bf16-rounded operands and add in fp32
+    (gpbm_backbone_backward); `saved` may come from a forward of either precision."""
+    prec = _prec(precision)
     dev = _dev(img)
     dims, depths = _dd(cfg)
     n = len(dims)
@@ -354,8 +414,9 @@ def backbone_backward(params, saved, img, g_feat, cfg, alloc=None):
     gt = _table(grads, shapes, dev, "grads")
     d_img = alloc("img", (B, 3, S, S))
     L = _lib.load()
-    nbytes = L.gpb_backbone_backward_workspace(_ints(dims), _ints(depths), n, B, S)
+    nbytes = _query(L, "backbone_backward_workspace", prec, _ints(dims), _ints(depths), n, B, S)
     ws = _ws(alloc, nbytes)
-    _call(dev, L.gpb_backbone_backward, "gpb_backbone_backward", pt, vt, img.data_ptr(), g_feat.data_ptr(), _ints(dims), _ints(depths), n, B, S,
-          gt, d_img.data_ptr(), ws.data_ptr(), nbytes, _stream(dev))
+    fn, name, tail = _entry(L, "backbone_backward", prec)
+    _call(dev, fn, name, pt, vt, img.data_ptr(), g_feat.data_ptr(), _ints(dims), _ints(depths), n, B, S,
+          gt, d_img.data_ptr(), ws.data_ptr(), nbytes, _stream(dev), *tail)
     return grads, d_img

@@ -15,10 +15,16 @@
 // at a time, which is loaded once and feeds every output row of the tile whose window holds it: (DW_TH + 6)(DW_TW + 6) loads for
 // DW_TH DW_TW outputs, 7 per output in the place of 49.  dW: 49 + 1 accumulators per lane over a chunk of rows.
 //
+// Precision (include/givepose_bbgrad_bf16.h, gpbm_*): the six dense contractions of a block go through gemm_p, which runs the fp32 chain
+// above or, for GPB_PREC_BF16, the bf16-operand form of the same functor GEMM (grad_gemm_bf16.hpp) with the same views, store functors and
+// workspace layout.  The patch convs, the row sums and everything that is not a contraction are fp32 in both modes.
+//
 // There is no atomic in this file.  The size queries and the entry points run the same host code: a Scratch in `dry` mode only
 // records what a run would take.
 #include "grad_gemm.hpp"
+#include "grad_gemm_bf16.hpp"
 #include "../../include/givepose_bbgrad.h"
+#include "../../include/givepose_bbgrad_bf16.h"
 
 namespace {
 
@@ -32,8 +38,8 @@ bool aligned256(const void* p) { return ((uintptr_t)p & 255) == 0; }
 
 // the workspace of a call: take() carves what lives to the end of the call, want() announces what one step needs behind that
 struct Scratch {
-    float* base; long size; bool dry; long used = 0, need = 0;
-    Scratch(void* ws, long long bytes, bool d) : base((float*)ws), size((long)(bytes / 4)), dry(d) {}
+    float* base; long size; bool dry; int prec; long used = 0, need = 0;      // prec: GPB_PREC_* of the block contractions (gemm_p)
+    Scratch(void* ws, long long bytes, bool d, int p = GPB_PREC_F32) : base((float*)ws), size((long)(bytes / 4)), dry(d), prec(p) {}
     float* take(long n) {
         float* p = base + used;
         used += up64(n);
@@ -51,6 +57,16 @@ int gemm_s(const AF& A, const BF& Bm, const EP& ep, long M, long N, long K, Scra
     if (sc.dry) return 0;
     return gemm(A, Bm, ep, M, N, K, sc.rest(), sc.rest_floats(), s, name);
 }
+
+// the six contractions of a block: in the call's precision, fp32 chains or bf16 operands with fp32 sums (grad_gemm_bf16.hpp)
+template <class AF, class BF, class EP>
+int gemm_p(const AF& A, const BF& Bm, const EP& ep, long M, long N, long K, Scratch& sc, hipStream_t s, const char* name) {
+    if (sc.prec == GPB_PREC_F32) return gemm_s(A, Bm, ep, M, N, K, sc, s, name);
+    sc.want(gemm_bf16_ws_floats(M, N, K));
+    if (sc.dry) return 0;
+    return gemm_bf16(A, Bm, ep, M, N, K, sc.rest(), sc.rest_floats(), s, name);
+}
+bool prec_ok(int p) { return p == GPB_PREC_F32 || p == GPB_PREC_BF16; }
 
 // ---------------------------------------------------------------------------------- views and store functors of this family
 struct Patch {       // non-overlapping p x p patches as rows (b,oh,ow) x columns (ci,kh,kw); sb, sc, sy, sx: element strides of b, ci, y, x
@@ -452,11 +468,11 @@ int block_forward(const float* x, const gpb_block_params& p, int N, int H, int W
         GPH_TRY((dw7_run<false, false>(x, p.dw_w, p.dw_b, NoRes{}, N, H, W, C, dwout, s, name)));
         GPH_TRY(ln_forward(dwout, p.ln_w, p.ln_b, rows, C, z, mean, rstd, false, s, name));
     }
-    GPH_TRY(gemm_s(MatRow{z, C}, MatCol{p.fc1_w, C}, EpFc1{h, a, C4, p.fc1_b}, rows, C4, C, sc, s, name));
+    GPH_TRY(gemm_p(MatRow{z, C}, MatCol{p.fc1_w, C}, EpFc1{h, a, C4, p.fc1_b}, rows, C4, C, sc, s, name));
     if (out_nchw)
-        GPH_TRY(gemm_s(MatRow{a, C4}, MatCol{p.fc2_w, C4}, EpFc2<true>{y2, x, p.fc2_b, p.gamma, out, C, H * W}, rows, C, C4, sc, s, name));
+        GPH_TRY(gemm_p(MatRow{a, C4}, MatCol{p.fc2_w, C4}, EpFc2<true>{y2, x, p.fc2_b, p.gamma, out, C, H * W}, rows, C, C4, sc, s, name));
     else
-        GPH_TRY(gemm_s(MatRow{a, C4}, MatCol{p.fc2_w, C4}, EpFc2<false>{y2, x, p.fc2_b, p.gamma, out, C, H * W}, rows, C, C4, sc, s, name));
+        GPH_TRY(gemm_p(MatRow{a, C4}, MatCol{p.fc2_w, C4}, EpFc2<false>{y2, x, p.fc2_b, p.gamma, out, C, H * W}, rows, C, C4, sc, s, name));
     sc.used = keep;
     return 0;
 }
@@ -482,14 +498,14 @@ int block_backward(const G& g, const float* x, const gpb_block_params& p, const 
     GPH_TRY(colsum_s(Prod<G>{g, y2, C}, rows, C, gr.gamma, sc, s, name));
     // fc2 with d y2 = g gamma never formed: the scale leaves the contractions, whose operands then stream under the MFMAs as plain
     // loads.  d W2 = gamma (g^T a) in the store functor, d b2 the row sum of g gamma, d h = g (gamma W2) GELU'(h) over a
-    GPH_TRY(gemm_s(Tr<G>{g}, MatRow{a, C4}, EpRowScaleM{gr.fc2_w, C4, p.gamma}, C, C4, rows, sc, s, name));
+    GPH_TRY(gemm_p(Tr<G>{g}, MatRow{a, C4}, EpRowScaleM{gr.fc2_w, C4, p.gamma}, C, C4, rows, sc, s, name));
     GPH_TRY(colsum_s(Scaled<G>{g, p.gamma}, rows, C, gr.fc2_b, sc, s, name));
     float* dh = a;
-    GPH_TRY(gemm_s(g, MatRow{w2s, C4}, EpGeluBack{dh, h, C4}, rows, C4, C, sc, s, name));
+    GPH_TRY(gemm_p(g, MatRow{w2s, C4}, EpGeluBack{dh, h, C4}, rows, C4, C, sc, s, name));
     // fc1
-    GPH_TRY(gemm_s(Tr<MatRow>{MatRow{dh, C4}}, MatRow{z, C}, EpRow{gr.fc1_w, C, nullptr, 0, 0}, C4, C, rows, sc, s, name));
+    GPH_TRY(gemm_p(Tr<MatRow>{MatRow{dh, C4}}, MatRow{z, C}, EpRow{gr.fc1_w, C, nullptr, 0, 0}, C4, C, rows, sc, s, name));
     GPH_TRY(colsum_s(MatRow{dh, C4}, rows, C4, gr.fc1_b, sc, s, name));
-    GPH_TRY(gemm_s(MatRow{dh, C4}, MatRow{p.fc1_w, C}, EpRow{dz, C, nullptr, 0, 0}, rows, C, C4, sc, s, name));
+    GPH_TRY(gemm_p(MatRow{dh, C4}, MatRow{p.fc1_w, C}, EpRow{dz, C, nullptr, 0, 0}, rows, C, C4, sc, s, name));
     // LayerNorm at the saved statistics, d dwout over z
     float* du = z;
     GPH_TRY(ln_backward(dz, dwout, mean, rstd, p.ln_w, rows, C, du, gr.ln_w, gr.ln_b, sc, s, name));
@@ -647,6 +663,88 @@ int net_backward(float* const* P, float* const* V, const float* img, const float
     GP_REQUIRE((dry).need == 0 || ((ws) && aligned256(ws) && (ws_bytes) / 4 >= (dry).need),                                      \
                "%s: workspace missing, unaligned or too small (%lld bytes, %ld needed)", name, (long long)(ws_bytes), 4 * (dry).need)
 
+// ---------------------------------------------------------------------------------- the entry points of the block and the backbone
+// One body serves the fp32 entry point and its precision-taking form: `name` is the caller's, `prec` a GPB_PREC_* value.
+long long block_workspace(int N, int H, int W, int C, int prec) {
+    if (!block_ok(N, H, W, C) || !prec_ok(prec)) return 0;
+    Scratch d(nullptr, 0, true, prec);
+    block_forward(nullptr, NO_BLOCK, N, H, W, C, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, d, nullptr, "");
+    block_backward(MatRow{nullptr, C}, nullptr, NO_BLOCK, nullptr, nullptr, nullptr, nullptr, nullptr, N, H, W, C, NO_BLOCK, nullptr, d, nullptr, "");
+    return 4LL * d.need;
+}
+
+int block_forward_save(const float* x, const gpb_block_params* params, int N, int H, int W, int C, float* dwout, float* mean, float* rstd,
+                       float* h, float* y2, float* out, void* ws, long long ws_bytes, void* stream, int prec, const char* name) {
+    GP_REQUIRE(prec_ok(prec), "%s: unknown precision %d (GPB_PREC_F32 or GPB_PREC_BF16)", name, prec);
+    GP_REQUIRE(x && block_complete(params) && dwout && mean && rstd && h && y2 && out, "%s: null pointer", name);
+    GP_REQUIRE(block_ok(N, H, W, C), "%s: bad shape N %d H %d W %d C %d (C must be a multiple of 64)", name, N, H, W, C);
+    GP_REQUIRE(ws && aligned256(ws) && ws_bytes >= block_workspace(N, H, W, C, prec), "%s: workspace missing, unaligned or too small", name);
+    Scratch sc(ws, ws_bytes, false, prec);
+    return block_forward(x, *params, N, H, W, C, dwout, mean, rstd, h, y2, out, false, sc, (hipStream_t)stream, name);
+}
+
+int block_backward_entry(const float* g, const float* x, const gpb_block_params* params, const float* dwout, const float* mean,
+                         const float* rstd, const float* h, const float* y2, int N, int H, int W, int C, const gpb_block_params* grads,
+                         float* dx, void* ws, long long ws_bytes, void* stream, int prec, const char* name) {
+    GP_REQUIRE(prec_ok(prec), "%s: unknown precision %d (GPB_PREC_F32 or GPB_PREC_BF16)", name, prec);
+    GP_REQUIRE(g && x && block_complete(params) && dwout && mean && rstd && h && y2 && block_complete(grads) && dx, "%s: null pointer", name);
+    GP_REQUIRE(dx != g, "%s: dx must not alias g", name);
+    GP_REQUIRE(block_ok(N, H, W, C), "%s: bad shape N %d H %d W %d C %d (C must be a multiple of 64)", name, N, H, W, C);
+    GP_REQUIRE(ws && aligned256(ws) && ws_bytes >= block_workspace(N, H, W, C, prec), "%s: workspace missing, unaligned or too small", name);
+    Scratch sc(ws, ws_bytes, false, prec);
+    return block_backward(MatRow{g, C}, x, *params, dwout, mean, rstd, h, y2, N, H, W, C, *grads, dx, sc, (hipStream_t)stream, name);
+}
+
+long long backbone_forward_workspace(const int* dims, const int* depths, int n_stages, int B, int S, int prec) {
+    Net net;
+    if (!net_ok(dims, depths, n_stages, B, S, net) || !prec_ok(prec)) return 0;
+    Scratch d(nullptr, 0, true, prec);
+    net_forward(nullptr, nullptr, net, nullptr, nullptr, d, nullptr, "");
+    return 4LL * d.need;
+}
+
+int backbone_forward_save(const float* img, float* const* params, const int* dims, const int* depths, int n_stages, int B, int S,
+                          float* const* saved, float* feat, void* ws, long long ws_bytes, void* stream, int prec, const char* name) {
+    Net net;
+    GP_REQUIRE(prec_ok(prec), "%s: unknown precision %d (GPB_PREC_F32 or GPB_PREC_BF16)", name, prec);
+    if (dims)
+        for (int s = 0; s < n_stages && s < GPB_MAX_STAGES; ++s)
+            GP_REQUIRE(dims[s] > 0 && dims[s] % 64 == 0, "%s: dims[%d] = %d is not a multiple of 64", name, s, dims[s]);
+    GP_REQUIRE(net_ok(dims, depths, n_stages, B, S, net), "%s: bad configuration (stages %d B %d S %d)", name, n_stages, B, S);
+    GP_REQUIRE(img && feat && table_complete(params, param_count(depths, n_stages)) && table_complete(saved, saved_count(net)),
+               "%s: null pointer", name);
+    GP_REQUIRE(ws && aligned256(ws) && ws_bytes >= backbone_forward_workspace(dims, depths, n_stages, B, S, prec),
+               "%s: workspace missing, unaligned or too small", name);
+    Scratch sc(ws, ws_bytes, false, prec);
+    return net_forward(img, params, net, saved, feat, sc, (hipStream_t)stream, name);
+}
+
+long long backbone_backward_workspace(const int* dims, const int* depths, int n_stages, int B, int S, int prec) {
+    Net net;
+    if (!net_ok(dims, depths, n_stages, B, S, net) || !prec_ok(prec)) return 0;
+    Scratch d(nullptr, 0, true, prec);
+    net_backward(nullptr, nullptr, nullptr, nullptr, net, nullptr, nullptr, d, nullptr, "");
+    return 4LL * d.need;
+}
+
+int backbone_backward_entry(float* const* params, float* const* saved, const float* img, const float* g_feat, const int* dims,
+                            const int* depths, int n_stages, int B, int S, float* const* grads, float* d_img, void* ws, long long ws_bytes,
+                            void* stream, int prec, const char* name) {
+    Net net;
+    GP_REQUIRE(prec_ok(prec), "%s: unknown precision %d (GPB_PREC_F32 or GPB_PREC_BF16)", name, prec);
+    if (dims)
+        for (int s = 0; s < n_stages && s < GPB_MAX_STAGES; ++s)
+            GP_REQUIRE(dims[s] > 0 && dims[s] % 64 == 0, "%s: dims[%d] = %d is not a multiple of 64", name, s, dims[s]);
+    GP_REQUIRE(net_ok(dims, depths, n_stages, B, S, net), "%s: bad configuration (stages %d B %d S %d)", name, n_stages, B, S);
+    const int np = param_count(depths, n_stages);
+    GP_REQUIRE(img && g_feat && d_img && table_complete(params, np) && table_complete(grads, np) && table_complete(saved, saved_count(net)),
+               "%s: null pointer", name);
+    GP_REQUIRE(ws && aligned256(ws) && ws_bytes >= backbone_backward_workspace(dims, depths, n_stages, B, S, prec),
+               "%s: workspace missing, unaligned or too small", name);
+    Scratch sc(ws, ws_bytes, false, prec);
+    return net_backward(params, saved, img, g_feat, net, grads, d_img, sc, (hipStream_t)stream, name);
+}
+
 }  // namespace
 
 extern "C" {
@@ -735,86 +833,104 @@ int gpb_patch_conv_backward(const float* dy, const float* x, const float* w, int
     return patch_backward(dy, x, w, N, H, W, Cin, Cout, p, nchw, dx, dw, db, sc, (hipStream_t)stream, name);
 }
 
-long long gpb_block_workspace(int N, int H, int W, int C) {
-    if (!block_ok(N, H, W, C)) return 0;
-    Scratch d(nullptr, 0, true);
-    block_forward(nullptr, NO_BLOCK, N, H, W, C, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, d, nullptr, "");
-    block_backward(MatRow{nullptr, C}, nullptr, NO_BLOCK, nullptr, nullptr, nullptr, nullptr, nullptr, N, H, W, C, NO_BLOCK, nullptr, d, nullptr, "");
-    return 4LL * d.need;
-}
+long long gpb_block_workspace(int N, int H, int W, int C) { return block_workspace(N, H, W, C, GPB_PREC_F32); }
 
 int gpb_block_forward_save(const float* x, const gpb_block_params* params, int N, int H, int W, int C, float* dwout, float* mean,
                            float* rstd, float* h, float* y2, float* out, void* ws, long long ws_bytes, void* stream) {
-    const char* name = "gpb_block_forward_save";
-    GP_REQUIRE(x && block_complete(params) && dwout && mean && rstd && h && y2 && out, "%s: null pointer", name);
-    GP_REQUIRE(block_ok(N, H, W, C), "%s: bad shape N %d H %d W %d C %d (C must be a multiple of 64)", name, N, H, W, C);
-    GP_REQUIRE(ws && aligned256(ws) && ws_bytes >= gpb_block_workspace(N, H, W, C), "%s: workspace missing, unaligned or too small", name);
-    Scratch sc(ws, ws_bytes, false);
-    return block_forward(x, *params, N, H, W, C, dwout, mean, rstd, h, y2, out, false, sc, (hipStream_t)stream, name);
+    return block_forward_save(x, params, N, H, W, C, dwout, mean, rstd, h, y2, out, ws, ws_bytes, stream, GPB_PREC_F32, "gpb_block_forward_save");
 }
 
 int gpb_block_backward(const float* g, const float* x, const gpb_block_params* params, const float* dwout, const float* mean,
                        const float* rstd, const float* h, const float* y2, int N, int H, int W, int C, const gpb_block_params* grads,
                        float* dx, void* ws, long long ws_bytes, void* stream) {
-    const char* name = "gpb_block_backward";
-    GP_REQUIRE(g && x && block_complete(params) && dwout && mean && rstd && h && y2 && block_complete(grads) && dx, "%s: null pointer", name);
-    GP_REQUIRE(dx != g, "%s: dx must not alias g", name);
-    GP_REQUIRE(block_ok(N, H, W, C), "%s: bad shape N %d H %d W %d C %d (C must be a multiple of 64)", name, N, H, W, C);
-    GP_REQUIRE(ws && aligned256(ws) && ws_bytes >= gpb_block_workspace(N, H, W, C), "%s: workspace missing, unaligned or too small", name);
-    Scratch sc(ws, ws_bytes, false);
-    return block_backward(MatRow{g, C}, x, *params, dwout, mean, rstd, h, y2, N, H, W, C, *grads, dx, sc, (hipStream_t)stream, name);
+    return block_backward_entry(g, x, params, dwout, mean, rstd, h, y2, N, H, W, C, grads, dx, ws, ws_bytes, stream, GPB_PREC_F32,
+                                "gpb_block_backward");
 }
 
 int gpb_param_count(const int* depths, int n_stages) { return param_count(depths, n_stages); }
 
 long long gpb_backbone_forward_workspace(const int* dims, const int* depths, int n_stages, int B, int S) {
-    Net net;
-    if (!net_ok(dims, depths, n_stages, B, S, net)) return 0;
-    Scratch d(nullptr, 0, true);
-    net_forward(nullptr, nullptr, net, nullptr, nullptr, d, nullptr, "");
-    return 4LL * d.need;
+    return backbone_forward_workspace(dims, depths, n_stages, B, S, GPB_PREC_F32);
 }
 
 int gpb_backbone_forward_save(const float* img, float* const* params, const int* dims, const int* depths, int n_stages, int B, int S,
                               float* const* saved, float* feat, void* ws, long long ws_bytes, void* stream) {
-    const char* name = "gpb_backbone_forward_save";
-    Net net;
-    if (dims)
-        for (int s = 0; s < n_stages && s < GPB_MAX_STAGES; ++s)
-            GP_REQUIRE(dims[s] > 0 && dims[s] % 64 == 0, "%s: dims[%d] = %d is not a multiple of 64", name, s, dims[s]);
-    GP_REQUIRE(net_ok(dims, depths, n_stages, B, S, net), "%s: bad configuration (stages %d B %d S %d)", name, n_stages, B, S);
-    GP_REQUIRE(img && feat && table_complete(params, param_count(depths, n_stages)) && table_complete(saved, saved_count(net)),
-               "%s: null pointer", name);
-    GP_REQUIRE(ws && aligned256(ws) && ws_bytes >= gpb_backbone_forward_workspace(dims, depths, n_stages, B, S),
-               "%s: workspace missing, unaligned or too small", name);
-    Scratch sc(ws, ws_bytes, false);
-    return net_forward(img, params, net, saved, feat, sc, (hipStream_t)stream, name);
+    return backbone_forward_save(img, params, dims, depths, n_stages, B, S, saved, feat, ws, ws_bytes, stream, GPB_PREC_F32,
+                                 "gpb_backbone_forward_save");
 }
 
 long long gpb_backbone_backward_workspace(const int* dims, const int* depths, int n_stages, int B, int S) {
-    Net net;
-    if (!net_ok(dims, depths, n_stages, B, S, net)) return 0;
-    Scratch d(nullptr, 0, true);
-    net_backward(nullptr, nullptr, nullptr, nullptr, net, nullptr, nullptr, d, nullptr, "");
-    return 4LL * d.need;
+    return backbone_backward_workspace(dims, depths, n_stages, B, S, GPB_PREC_F32);
 }
 
 int gpb_backbone_backward(float* const* params, float* const* saved, const float* img, const float* g_feat, const int* dims,
                           const int* depths, int n_stages, int B, int S, float* const* grads, float* d_img, void* ws, long long ws_bytes,
                           void* stream) {
-    const char* name = "gpb_backbone_backward";
-    Net net;
-    if (dims)
-        for (int s = 0; s < n_stages && s < GPB_MAX_STAGES; ++s)
-            GP_REQUIRE(dims[s] > 0 && dims[s] % 64 == 0, "%s: dims[%d] = %d is not a multiple of 64", name, s, dims[s]);
-    GP_REQUIRE(net_ok(dims, depths, n_stages, B, S, net), "%s: bad configuration (stages %d B %d S %d)", name, n_stages, B, S);
-    const int np = param_count(depths, n_stages);
-    GP_REQUIRE(img && g_feat && d_img && table_complete(params, np) && table_complete(grads, np) && table_complete(saved, saved_count(net)),
-               "%s: null pointer", name);
-    GP_REQUIRE(ws && aligned256(ws) && ws_bytes >= gpb_backbone_backward_workspace(dims, depths, n_stages, B, S),
-               "%s: workspace missing, unaligned or too small", name);
-    Scratch sc(ws, ws_bytes, false);
-    return net_backward(params, saved, img, g_feat, net, grads, d_img, sc, (hipStream_t)stream, name);
+    return backbone_backward_entry(params, saved, img, g_feat, dims, depths, n_stages, B, S, grads, d_img, ws, ws_bytes, stream, GPB_PREC_F32,
+                                   "gpb_backbone_backward");
+}
+
+/* ---- the precision-taking forms (include/givepose_bbgrad_bf16.h) ---- */
+
+long long gpbm_matmul_bf16_workspace(int M, int N, int K) {
+    if (M <= 0 || N <= 0 || K <= 0) return 0;
+    return 4LL * up64(gemm_bf16_ws_floats(M, N, K));
+}
+
+int gpbm_matmul_bf16(const float* a, const float* b, int M, int N, int K, int trans_a, int trans_b, float* c, void* ws, long long ws_bytes,
+                     void* stream) {
+    const char* name = "gpbm_matmul_bf16";
+    GP_REQUIRE(a && b && c, "%s: null pointer", name);
+    GP_REQUIRE(M > 0 && N > 0 && K > 0 && (long)M * N < (1L << 40) && (long)M * K < (1L << 40) && (long)K * N < (1L << 40),
+               "%s: bad shape M %d N %d K %d", name, M, N, K);
+    const long need = gemm_bf16_ws_floats(M, N, K);
+    GP_REQUIRE(need == 0 || (ws && aligned256(ws) && ws_bytes / 4 >= need), "%s: workspace missing, unaligned or too small (%lld bytes, %ld needed)",
+               name, ws_bytes, 4 * need);
+    const EpRow ep{c, N, nullptr, 0, 0};
+    float* w = (float*)ws;
+    const long wf = (long)(ws_bytes / 4);
+    hipStream_t s = (hipStream_t)stream;
+    if (trans_a) {
+        if (trans_b) return gemm_bf16(MatCol{a, M}, MatCol{b, K}, ep, M, N, K, w, wf, s, name);
+        return gemm_bf16(MatCol{a, M}, MatRow{b, N}, ep, M, N, K, w, wf, s, name);
+    }
+    if (trans_b) return gemm_bf16(MatRow{a, K}, MatCol{b, K}, ep, M, N, K, w, wf, s, name);
+    return gemm_bf16(MatRow{a, K}, MatRow{b, N}, ep, M, N, K, w, wf, s, name);
+}
+
+long long gpbm_block_workspace(int N, int H, int W, int C, int precision) { return block_workspace(N, H, W, C, precision); }
+
+int gpbm_block_forward_save(const float* x, const gpb_block_params* params, int N, int H, int W, int C, float* dwout, float* mean,
+                            float* rstd, float* h, float* y2, float* out, void* ws, long long ws_bytes, void* stream, int precision) {
+    return block_forward_save(x, params, N, H, W, C, dwout, mean, rstd, h, y2, out, ws, ws_bytes, stream, precision, "gpbm_block_forward_save");
+}
+
+int gpbm_block_backward(const float* g, const float* x, const gpb_block_params* params, const float* dwout, const float* mean,
+                        const float* rstd, const float* h, const float* y2, int N, int H, int W, int C, const gpb_block_params* grads,
+                        float* dx, void* ws, long long ws_bytes, void* stream, int precision) {
+    return block_backward_entry(g, x, params, dwout, mean, rstd, h, y2, N, H, W, C, grads, dx, ws, ws_bytes, stream, precision,
+                                "gpbm_block_backward");
+}
+
+long long gpbm_backbone_forward_workspace(const int* dims, const int* depths, int n_stages, int B, int S, int precision) {
+    return backbone_forward_workspace(dims, depths, n_stages, B, S, precision);
+}
+
+int gpbm_backbone_forward_save(const float* img, float* const* params, const int* dims, const int* depths, int n_stages, int B, int S,
+                               float* const* saved, float* feat, void* ws, long long ws_bytes, void* stream, int precision) {
+    return backbone_forward_save(img, params, dims, depths, n_stages, B, S, saved, feat, ws, ws_bytes, stream, precision,
+                                 "gpbm_backbone_forward_save");
+}
+
+long long gpbm_backbone_backward_workspace(const int* dims, const int* depths, int n_stages, int B, int S, int precision) {
+    return backbone_backward_workspace(dims, depths, n_stages, B, S, precision);
+}
+
+int gpbm_backbone_backward(float* const* params, float* const* saved, const float* img, const float* g_feat, const int* dims,
+                           const int* depths, int n_stages, int B, int S, float* const* grads, float* d_img, void* ws, long long ws_bytes,
+                           void* stream, int precision) {
+    return backbone_backward_entry(params, saved, img, g_feat, dims, depths, n_stages, B, S, grads, d_img, ws, ws_bytes, stream, precision,
+                                   "gpbm_backbone_backward");
 }
 
 }  // extern "C"

@@ -229,6 +229,25 @@ class PoseNet(nn.Module):
             self._repack_mode = mode
         return self
 
+    # the precision of the backbone's recompute and backward (`backbone_backward`, and with it `head_grads_backbone` and `train_step`)
+    _backward_precision = "fp32"
+
+    @property
+    def backward_precision(self):
+        """"fp32" (the default) or "bf16": see `set_backward_precision`."""
+        return self._backward_precision
+
+    def set_backward_precision(self, mode):
+        """"fp32" (the default): the backbone's recompute and backward are the fp32 chains of the gpb_ family.
+        "bf16": the six dense contractions of every ConvNeXt block multiply bf16-rounded operands and add in fp32, as
+        torch.autocast(bfloat16) does elsewhere (givepose_amd.bb_grad, precision="bf16"; include/givepose_bbgrad_bf16.h); no loss scaling
+        is needed.  Everything else in the chain -- the heads, the encoder, the loss, the optimiser, the forward -- is unchanged, and
+        switching back to "fp32" gives the bits of before.  Nothing is cached per mode: the switch costs nothing."""
+        if mode not in ("fp32", "bf16"):
+            raise ValueError(f"set_backward_precision: {mode!r}, expected 'fp32' or 'bf16'")
+        self._backward_precision = mode
+        return self
+
     def _pack_device(self, device):
         """`_pack` under set_repack("device"): allocates the packed tensors (the keys, shapes and dtypes of `_pack`) and fills them on the
         device.  The parameters must be contiguous float32 on `device` (ValueError names the first that is not)."""
@@ -1418,7 +1437,9 @@ class PoseNet(nn.Module):
         -> {"param_grads": {state_dict name: fp32 gradient in that parameter's own shape} for every backbone.* tensor, in state_dict
             order, "img": (B,3,S,S), the gradient of the image, "outputs": {"feat": (B,Cfeat,S/32,S/32)} of the fp32 recompute};
         return_saved adds "saved" (givepose_amd.bb_grad.saved_shapes: 176.7 MB per crop for ConvNeXt-Base at 256 x 256).
-        There is no atomic on this path: two calls give equal bits.  The fp32 parameters are cached as `_module_params_f32` caches them."""
+        There is no atomic on this path: two calls give equal bits.  The fp32 parameters are cached as `_module_params_f32` caches them.
+        Under set_backward_precision("bf16") the block contractions of both passes take bf16-rounded operands (fp32 sums); parameters,
+        saved tensors and results stay fp32."""
         from . import bb_grad
         self._backbone_backward_supported("backbone_backward")
         dev = torch.device(device)
@@ -1426,8 +1447,8 @@ class PoseNet(nn.Module):
         P = self._module_params_f32("backbone", bb_grad.PARAM_KEYS(self.cfg), dev)
         img = torch.as_tensor(img).to(dev).to(torch.float32).contiguous()
         g_feat = torch.as_tensor(g_feat).to(dev).to(torch.float32).contiguous()
-        saved, feat = bb_grad.backbone_forward_save(img, P, self.cfg)
-        grads, d_img = bb_grad.backbone_backward(P, saved, img, g_feat, self.cfg)
+        saved, feat = bb_grad.backbone_forward_save(img, P, self.cfg, precision=self._backward_precision)
+        grads, d_img = bb_grad.backbone_backward(P, saved, img, g_feat, self.cfg, precision=self._backward_precision)
         res = {"param_grads": {"backbone." + k: v for k, v in grads.items()}, "img": d_img, "outputs": {"feat": feat}}
         if return_saved:
             res["saved"] = saved
