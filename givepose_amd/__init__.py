@@ -57,6 +57,10 @@ Public surface mirrors the reference for this path:
                      ConvNeXt block multiply bf16-rounded operands on v_mfma_f32_32x32x16_bf16 and add in fp32, everything else
                      stays the fp32 code; "fp32" (the default) is bit for bit what it was (csrc/grad_gemm_bf16.hpp,
                      include/givepose_bbgrad_bf16.h)
+  PoseNet.set_backward_precision(mode, xyz_heads="fp32" | "bf16"), PoseNet.xyz_backward_precision, precision= of xyz_grad's conv, transposed-conv and head calls
+                     the same for the two coordinate heads: under "bf16" the 21 contractions of a head's 3x3 layers (forward, dX, dW)
+                     take bf16-rounded operands in the recompute and in the backward; GroupNorm + GELU, the bilinear x2 and the 1x1
+                     output conv stay fp32 (csrc/xyz_conv_prec.hpp, include/givepose_xyzgrad_bf16.h)
   GradAccumulator, train_step(accumulator=, accumulate=, micro_step=, group=)
                      FLAGS.accumulate and the gradient all-reduce across ranks (engine/train.py:117-131): the micro-steps' gradients
                      added, scaled and clipped in place in one flat device buffer in three launches, exchanged between ranks by one

@@ -187,6 +187,16 @@ XYZGRAD_PROTOTYPES = {
 }
 GPX_FEAT, GPX_GROUPS, GPX_LAYERS = 256, 32, 7
 
+# its mixed-precision forms (include/givepose_xyzgrad_bf16.h, prefix gpxm_; tests/test_xyz_bf16_cpu.py checks both ways): a trailing
+# `precision` on the conv, transposed-conv and head entry points and their size queries
+GPX_PREC_F32, GPX_PREC_BF16 = 0, 1
+XYZGRAD_BF16_PROTOTYPES = {
+    "gpxm_" + name[len("gpx_"):]: (XYZGRAD_PROTOTYPES[name][0] + [c_int], XYZGRAD_PROTOTYPES[name][1])
+    for name in ("gpx_conv3x3s1_workspace", "gpx_conv3x3s1_forward", "gpx_conv3x3s1_backward", "gpx_deconv3x3s2_workspace",
+                 "gpx_deconv3x3s2_forward", "gpx_deconv3x3s2_backward", "gpx_xyz_forward_workspace", "gpx_xyz_forward_save",
+                 "gpx_xyz_backward_workspace", "gpx_xyz_backward")
+}
+
 
 # the map-encoder backward family (include/givepose_encgrad.h, prefix gpe_; tests/test_enc_backward_cpu.py checks both ways)
 class EncLayerParams(Structure):      # gpe_layer_params: the 16 tensors of one encoder layer, weights or their gradients
@@ -380,7 +390,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (argtypes, restype) in (list(PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items())
                                       + list(GRAD_PROTOTYPES.items()) + list(HEADGRAD_PROTOTYPES.items())
-                                      + list(XYZGRAD_PROTOTYPES.items()) + list(ENCGRAD_PROTOTYPES.items())
+                                      + list(XYZGRAD_PROTOTYPES.items()) + list(XYZGRAD_BF16_PROTOTYPES.items()) + list(ENCGRAD_PROTOTYPES.items())
                                       + list(BBGRAD_PROTOTYPES.items()) + list(BBGRAD_BF16_PROTOTYPES.items()) + list(OPTIM_PROTOTYPES.items())
                                       + list(SIZEGRAD_PROTOTYPES.items()) + list(ACCUM_PROTOTYPES.items())
                                       + list(REPACK_PROTOTYPES.items()) + list(TRAINDATA_PROTOTYPES.items())):

@@ -48,7 +48,8 @@ def build(force=False, verbose=True):
             os.path.join(HERE, "..", "include", "givepose_optim.h"), os.path.join(HERE, "..", "include", "givepose_sizegrad.h"),
             os.path.join(HERE, "..", "include", "givepose_accum.h"), os.path.join(HERE, "..", "include", "givepose_repack.h"),
             os.path.join(HERE, "..", "include", "givepose_traindata.h"), os.path.join(CSRC, "grad_gemm.hpp"), os.path.join(CSRC, "grad_gemm_bf16.hpp"),
-            os.path.join(HERE, "..", "include", "givepose_bbgrad_bf16.h")]
+            os.path.join(HERE, "..", "include", "givepose_bbgrad_bf16.h"), os.path.join(CSRC, "xyz_conv_prec.hpp"),
+            os.path.join(HERE, "..", "include", "givepose_xyzgrad_bf16.h")]
     objs, procs = [], []
     for src in SOURCES:
         s, o = os.path.join(CSRC, src), os.path.join(OBJ, src.replace(".hip", ".o"))

@@ -51,6 +51,27 @@ template <bool IS_B, class F> struct Bf16Plain { static constexpr bool value = f
 template <> struct Bf16Plain<false, MatRow> { static constexpr bool value = true; };
 template <> struct Bf16Plain<true, MatCol> { static constexpr bool value = true; };
 
+// A view whose k is adjacent in memory only inside a stretch (a channel of a crop) may give a group of four k-neighbours in one
+// 16-byte load as well: get() fills q and answers true when the whole group lies inside one stretch, and answers false where it does
+// not (a crop boundary), in which case the group is fetched element by element through the view.  Which elements are read, and so
+// every bit of the result, is the same either way.  (The same for the stride-1 window as B -- a row of a map, at a tap shift -- was
+// measured slower than the element-wise fetch and is not kept: DESIGN.md 1k.)  GP_BF16_WIDE_MASK (investigation builds only,
+// givepose_amd/build.py GP_EXTRA_HIPCC_FLAGS) switches specialisations off for A/B timing: bit 0 Tr<Nchw> as A, bit 1 the stride-1
+// window as A (Bf16Rows below, specialised in xyz_conv_prec.hpp).
+#ifndef GP_BF16_WIDE_MASK
+#define GP_BF16_WIDE_MASK 3
+#endif
+template <bool IS_B, class F> struct Bf16Wide { static constexpr bool value = false; };
+template <> struct Bf16Wide<false, Tr<Nchw>> {      // A(m, k) = p[(b C + m) HW + px], k = (b, px): four pixels of one channel of one crop
+    static constexpr bool value = (GP_BF16_WIDE_MASK & 1) != 0;
+    static __device__ __forceinline__ bool get(const Tr<Nchw>& f, int m, int k, f32x4& q) {
+        const int HW = f.f.HW, b = k / HW, px = k - b * HW;
+        if (px + 3 >= HW) return false;
+        __builtin_memcpy(&q, f.f.p + (((long)b * f.f.C + m) * HW + px), 16);
+        return true;
+    }
+};
+
 template <bool IS_B, bool KFAST, class F>
 __device__ __forceinline__ void bf16_fetch(const F& f, int mn0, int MN, int k0, int kend, float (&v)[16]) {
 #pragma unroll
@@ -64,6 +85,15 @@ __device__ __forceinline__ void bf16_fetch(const F& f, int mn0, int MN, int k0, 
                 __builtin_memcpy(&q, f.p + ((long)gmn * f.ld + gk), 16);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) v[4 * i + j] = q[j];
+            } else if constexpr (KFAST && Bf16Wide<IS_B, F>::value) {
+                f32x4 q;
+                if (Bf16Wide<IS_B, F>::get(f, gmn, gk, q)) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) v[4 * i + j] = q[j];
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) v[4 * i + j] = bf16_operand<IS_B>(f, gmn, gk + j);
+                }
             } else {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) v[4 * i + j] = bf16_operand<IS_B>(f, gmn, gk + j);
@@ -73,6 +103,28 @@ __device__ __forceinline__ void bf16_fetch(const F& f, int mn0, int MN, int k0, 
             for (int j = 0; j < 4; ++j) v[4 * i + j] = (gmn < MN && gk + j < kend) ? bf16_operand<IS_B>(f, gmn, gk + j) : 0.0f;
         }
     }
+}
+
+// An A operand fetched with m on the lane keeps a thread on ONE row m for the whole contraction, and its k -- (t >> 7) * 4 + 8 i + j on top
+// of the step's k0 -- is the same in every lane of a wave.  A view can therefore keep what depends on the row in a per-thread State
+// formed once in front of the k loop (init), and form what depends on k in scalar registers (get); the k offset of the wave is read
+// through readfirstlane so that the compiler knows it to be uniform.  A row outside the matrix gets a State whose elements are all 0.
+template <class F> struct Bf16Rows {
+    static constexpr bool value = false;
+    struct State {};
+    static __device__ __forceinline__ State init(const F&, int, int) { return {}; }
+};
+
+template <class F>
+__device__ __forceinline__ void bf16_fetch_rows(const F& f, const typename Bf16Rows<F>::State& st, int k0, int kend, float (&v)[16]) {
+    const int kq = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 7)) * 4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int gk = k0 + kq + 8 * i + j;
+            v[4 * i + j] = gk < kend ? Bf16Rows<F>::get(f, st, gk) : 0.0f;
+        }
 }
 
 template <bool KFAST>
@@ -94,7 +146,7 @@ template <class AF, class BF, class EP>
 __global__ __launch_bounds__(WG) void gemm_bf16_kernel(AF A, BF Bm, EP ep, int M, int N, int K, int kchunk, float* __restrict__ part) {
     __shared__ __attribute__((aligned(16))) __bf16 As[2][HM][HLD];
     __shared__ __attribute__((aligned(16))) __bf16 Bs[2][HN][HLD];
-    constexpr bool AK = AF::FAST_C, BK = !BF::FAST_C;
+    constexpr bool AK = AF::FAST_C, BK = !BF::FAST_C, AROWS = !AK && Bf16Rows<AF>::value;
     const int m0 = blockIdx.x * HM, n0 = blockIdx.y * HN;
     const int kbeg = blockIdx.z * kchunk, kend = min(K, kbeg + kchunk);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
@@ -107,7 +159,12 @@ __global__ __launch_bounds__(WG) void gemm_bf16_kernel(AF A, BF Bm, EP ep, int M
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
     float ra[16], rb[16];
-    bf16_fetch<false, AK>(A, m0, M, kbeg, kend, ra);
+    const typename Bf16Rows<AF>::State arow = Bf16Rows<AF>::init(A, blockIdx.x * HM + (threadIdx.x & 127), M);
+    auto fetch_a = [&](int k0) {
+        if constexpr (AROWS) bf16_fetch_rows(A, arow, k0, kend, ra);
+        else bf16_fetch<false, AK>(A, m0, M, k0, kend, ra);
+    };
+    fetch_a(kbeg);
     bf16_fetch<true, BK>(Bm, n0, N, kbeg, kend, rb);
     bf16_put<AK>(As[0], ra);
     bf16_put<BK>(Bs[0], rb);
@@ -116,7 +173,7 @@ __global__ __launch_bounds__(WG) void gemm_bf16_kernel(AF A, BF Bm, EP ep, int M
     for (int k0 = kbeg; k0 < kend; k0 += HK) {
         const bool more = k0 + HK < kend;
         if (more) {
-            bf16_fetch<false, AK>(A, m0, M, k0 + HK, kend, ra);
+            fetch_a(k0 + HK);
             bf16_fetch<true, BK>(Bm, n0, N, k0 + HK, kend, rb);
         }
 #pragma unroll

@@ -6,7 +6,13 @@
 // (GatherDY) with the input in the role of dY, its dX is the stride-2 conv (Im2col) of dY, its dW the stride-2 conv's dW with the
 // operand roles exchanged -- and its (Cin,Cout,3,3) weight is the OIHW weight of that stride-2 conv as it stands, so WeightDx,
 // MatCol and EpRow address it and its gradient directly.
+//
+// Precision (include/givepose_xyzgrad_bf16.h, gpxm_*): the 21 contractions of the 3x3 layers go through gemm_px (xyz_conv_prec.hpp), which
+// runs the fp32 chain or, for GPX_PREC_BF16, the bf16-operand form of the same functor GEMM with the same views and store functors.  The
+// 1x1 output conv, GroupNorm + GELU, the bilinear x2 and every reduction are fp32 in both.  The gpx_ entry points are the same bodies at
+// GPX_PREC_F32.
 #include "grad_gemm.hpp"
+#include "xyz_conv_prec.hpp"
 #include "../../include/givepose_xyzgrad.h"
 
 namespace {
@@ -14,20 +20,7 @@ namespace {
 constexpr int FEAT = GPX_FEAT, GROUPS = GPX_GROUPS, LAYERS = GPX_LAYERS;
 
 // ---------------------------------------------------------------------------------- views and stores of this family
-// (B,C,H,H) as rows (b,h,w) x columns (c,kh,kw): the element at (h - 1 + kh, w - 1 + kw) -- the im2col view of a stride-1 pad-1 conv
-// input -- or with flip at (h + 1 - kh, w + 1 - kw) -- the gathered view of its output gradient --, an exact 0 outside the map.
-// The tile loader keeps a thread on one row for a whole contraction, so the compiler hoists the divisions of r out of the k loop.
-struct WindowS1 {
-    const float* p; int C, H, flip;
-    static constexpr bool FAST_C = false;
-    __device__ __forceinline__ float operator()(int r, int c) const {
-        const int hw = H * H, b = r / hw, px = r - b * hw, h = px / H, w = px - h * H;
-        const int ch = c / 9, t0 = c - ch * 9, t = flip ? 8 - t0 : t0, kh = t / 3, kw = t - kh * 3;
-        const int y = h - 1 + kh, x = w - 1 + kw;
-        if ((unsigned)y >= (unsigned)H || (unsigned)x >= (unsigned)H) return 0.0f;
-        return p[(((long)b * C + ch) * H + y) * H + x];
-    }
-};
+// WindowS1, the view of the stride-1 conv, lives in xyz_conv_prec.hpp
 struct EpNchwBias {  // rows (b, pixel) -> C (B,Cc,HW), plus bias[n]
     float* C; int Cc, HW; const float* bias;
     static constexpr bool M_FAST = true;
@@ -41,58 +34,60 @@ long max2(long a, long b) { return a > b ? a : b; }
 bool aligned256(const void* p) { return ((uintptr_t)p & 255) == 0; }
 
 // ---------------------------------------------------------------------------------- 3x3 stride-1 pad-1 conv
-long conv_s1_ws_floats(long B, long Cin, long Cout, long H) {
+long conv_s1_ws_floats(long B, long Cin, long Cout, long H, int prec) {
     const long m = B * H * H;
-    return max2(gemm_ws_floats(m, Cout, Cin * 9), max2(gemm_ws_floats(Cout, Cin * 9, m), gemm_ws_floats(m, Cin, Cout * 9)));
+    return max2(gemm_px_ws_floats(prec, m, Cout, Cin * 9),
+                max2(gemm_px_ws_floats(prec, Cout, Cin * 9, m), gemm_px_ws_floats(prec, m, Cin, Cout * 9)));
 }
 bool conv_shape_ok(long B, long Cin, long Cout, long H) {
     return B > 0 && Cin > 0 && Cout > 0 && H > 0 && H <= 4096 && B * H * H < (1L << 28) && Cin <= 65536 && Cout <= 65536;
 }
 
 int conv_s1_forward(const float* X, const float* Wt, int B, int Cin, int Cout, int H, float* Y, float* ws, long wf, hipStream_t s,
-                    const char* name) {
+                    int prec, const char* name) {
     GP_REQUIRE(X && Wt && Y && conv_shape_ok(B, Cin, Cout, H), "%s: bad arguments (B %d Cin %d Cout %d H %d)", name, B, Cin, Cout, H);
-    return gemm(WindowS1{X, Cin, H, 0}, MatCol{Wt, (long)Cin * 9}, EpNchw{Y, Cout, H * H, nullptr}, (long)B * H * H, Cout, (long)Cin * 9, ws,
-                wf, s, name);
+    return gemm_px(prec, WindowS1{X, Cin, H, 0}, MatCol{Wt, (long)Cin * 9}, EpNchw{Y, Cout, H * H, nullptr}, (long)B * H * H, Cout,
+                   (long)Cin * 9, ws, wf, s, name);
 }
 
 int conv_s1_backward(const float* dY, const float* X, const float* Wt, int B, int Cin, int Cout, int H, float* dX, float* dW, float* ws,
-                     long wf, hipStream_t s, const char* name) {
+                     long wf, hipStream_t s, int prec, const char* name) {
     GP_REQUIRE(dY && conv_shape_ok(B, Cin, Cout, H), "%s: bad arguments (B %d Cin %d Cout %d H %d)", name, B, Cin, Cout, H);
     GP_REQUIRE((!dW || X) && (!dX || Wt), "%s: dW needs X, dX needs the weights", name);
     if (dW)      // (Cout x m) (m x Cin 9), m = (b,oh,ow)
-        GPH_TRY(gemm(Tr<Nchw>{Nchw{dY, Cout, H * H}}, WindowS1{X, Cin, H, 0}, EpRow{dW, (long)Cin * 9, nullptr, 0, 0}, Cout, (long)Cin * 9,
-                     (long)B * H * H, ws, wf, s, name));
+        GPH_TRY(gemm_px(prec, Tr<Nchw>{Nchw{dY, Cout, H * H}}, WindowS1{X, Cin, H, 0}, EpRow{dW, (long)Cin * 9, nullptr, 0, 0}, Cout,
+                        (long)Cin * 9, (long)B * H * H, ws, wf, s, name));
     if (dX)      // ((b,ih,iw) x (co,kh,kw)) ((co,kh,kw) x ci)
-        GPH_TRY(gemm(WindowS1{dY, Cout, H, 1}, WeightDx{Wt, Cin}, EpNchw{dX, Cin, H * H, nullptr}, (long)B * H * H, Cin, (long)Cout * 9, ws, wf,
-                     s, name));
+        GPH_TRY(gemm_px(prec, WindowS1{dY, Cout, H, 1}, WeightDx{Wt, Cin}, EpNchw{dX, Cin, H * H, nullptr}, (long)B * H * H, Cin,
+                        (long)Cout * 9, ws, wf, s, name));
     return 0;
 }
 
 // ---------------------------------------------------------------------------------- 3x3 stride-2 transposed conv
 // X (B,Cin,H,H), Wt (Cin,Cout,3,3), Y (B,Cout,2H,2H).  In the stride-2 conv that maps Y's shape to X's, Wt is the OIHW weight.
-long deconv_ws_floats(long B, long Cin, long Cout, long H) {
+long deconv_ws_floats(long B, long Cin, long Cout, long H, int prec) {
     const long m = B * H * H;
-    return max2(gemm_ws_floats(4 * m, Cout, Cin * 9), max2(gemm_ws_floats(m, Cin, Cout * 9), gemm_ws_floats(Cin, Cout * 9, m)));
+    return max2(gemm_px_ws_floats(prec, 4 * m, Cout, Cin * 9),
+                max2(gemm_px_ws_floats(prec, m, Cin, Cout * 9), gemm_px_ws_floats(prec, Cin, Cout * 9, m)));
 }
 
 int deconv_forward(const float* X, const float* Wt, int B, int Cin, int Cout, int H, float* Y, float* ws, long wf, hipStream_t s,
-                   const char* name) {
+                   int prec, const char* name) {
     GP_REQUIRE(X && Wt && Y && conv_shape_ok(B, Cin, Cout, 2L * H), "%s: bad arguments (B %d Cin %d Cout %d H %d)", name, B, Cin, Cout, H);
-    return gemm(GatherDY{X, Cin, 2 * H, H}, WeightDx{Wt, Cout}, EpNchw{Y, Cout, 4 * H * H, nullptr}, (long)B * 4 * H * H, Cout, (long)Cin * 9,
-                ws, wf, s, name);
+    return gemm_px(prec, GatherDY{X, Cin, 2 * H, H}, WeightDx{Wt, Cout}, EpNchw{Y, Cout, 4 * H * H, nullptr}, (long)B * 4 * H * H, Cout,
+                   (long)Cin * 9, ws, wf, s, name);
 }
 
 int deconv_backward(const float* dY, const float* X, const float* Wt, int B, int Cin, int Cout, int H, float* dX, float* dW, float* ws,
-                    long wf, hipStream_t s, const char* name) {
+                    long wf, hipStream_t s, int prec, const char* name) {
     GP_REQUIRE(dY && conv_shape_ok(B, Cin, Cout, 2L * H), "%s: bad arguments (B %d Cin %d Cout %d H %d)", name, B, Cin, Cout, H);
     GP_REQUIRE((!dW || X) && (!dX || Wt), "%s: dW needs X, dX needs the weights", name);
     if (dW)      // (Cin x m) (m x Cout 9), m = (b,ih,iw): rows (ci), columns (co,kh,kw) -- the weight's own order
-        GPH_TRY(gemm(Tr<Nchw>{Nchw{X, Cin, H * H}}, Im2col{dY, Cout, 2 * H, H}, EpRow{dW, (long)Cout * 9, nullptr, 0, 0}, Cin, (long)Cout * 9,
-                     (long)B * H * H, ws, wf, s, name));
+        GPH_TRY(gemm_px(prec, Tr<Nchw>{Nchw{X, Cin, H * H}}, Im2col{dY, Cout, 2 * H, H}, EpRow{dW, (long)Cout * 9, nullptr, 0, 0}, Cin,
+                        (long)Cout * 9, (long)B * H * H, ws, wf, s, name));
     if (dX)      // ((b,ih,iw) x (co,kh,kw)) ((co,kh,kw) x ci)
-        GPH_TRY(gemm(Im2col{dY, Cout, 2 * H, H}, MatCol{Wt, (long)Cout * 9}, EpNchw{dX, Cin, H * H, nullptr}, (long)B * H * H, Cin,
-                     (long)Cout * 9, ws, wf, s, name));
+        GPH_TRY(gemm_px(prec, Im2col{dY, Cout, 2 * H, H}, MatCol{Wt, (long)Cout * 9}, EpNchw{dX, Cin, H * H, nullptr}, (long)B * H * H, Cin,
+                        (long)Cout * 9, ws, wf, s, name));
     return 0;
 }
 
@@ -382,9 +377,9 @@ bool saved_complete(const gpx_xyz_saved* v) {
 }
 bool head_shape_ok(long B, long Cin, long H0) { return B > 0 && B <= 4096 && Cin > 0 && Cin <= 8192 && H0 > 0 && H0 <= 64 && B * 64 * H0 * H0 < (1L << 28); }
 
-long head_fwd_ws_floats(long B, long Cin, long H0) {
-    long w = gemm_ws_floats(B * 4 * H0 * H0, FEAT, Cin * 9);
-    for (int l = 1; l < LAYERS; ++l) w = max2(w, gemm_ws_floats(B * MUL[l] * MUL[l] * H0 * H0, FEAT, FEAT * 9));
+long head_fwd_ws_floats(long B, long Cin, long H0, int prec) {
+    long w = gemm_px_ws_floats(prec, B * 4 * H0 * H0, FEAT, Cin * 9);
+    for (int l = 1; l < LAYERS; ++l) w = max2(w, gemm_px_ws_floats(prec, B * MUL[l] * MUL[l] * H0 * H0, FEAT, FEAT * 9));
     w = max2(w, conv1x1_fwd_ws_floats(B, FEAT, 3, 64 * H0 * H0));
     return up64(w);
 }
@@ -393,56 +388,144 @@ long head_fwd_ws_floats(long B, long Cin, long H0) {
 struct BwdLayout {
     long p, q, scratch, scratch_floats, total;
 };
-BwdLayout bwd_layout(long B, long Cin, long H0) {
+BwdLayout bwd_layout(long B, long Cin, long H0, int prec) {
     BwdLayout L;
     const long big = up64(B * FEAT * 64 * H0 * H0);
     L.p = 0;
     L.q = big;
     L.scratch = 2 * big;
-    long w = max2(deconv_ws_floats(B, Cin, FEAT, H0), gn_bwd_ws_floats(B, FEAT));
-    for (int l = 1; l < LAYERS; ++l) w = max2(w, conv_s1_ws_floats(B, FEAT, FEAT, MUL[l] * H0));
+    long w = max2(deconv_ws_floats(B, Cin, FEAT, H0, prec), gn_bwd_ws_floats(B, FEAT));
+    for (int l = 1; l < LAYERS; ++l) w = max2(w, conv_s1_ws_floats(B, FEAT, FEAT, MUL[l] * H0, prec));
     w = max2(w, conv1x1_bwd_ws_floats(B, FEAT, 3, 64 * H0 * H0));
     L.scratch_floats = up64(w);
     L.total = L.scratch + L.scratch_floats;
     return L;
 }
 
+// ---------------------------------------------------------------------------------- the entry points' bodies
+// One body serves a gpx_ entry point and its precision-taking form: `name` is the caller's, `prec` a GPX_PREC_* value.
+#define XYZ_PREC_REQUIRE(prec, name) GP_REQUIRE(xyz_prec_ok(prec), "%s: unknown precision %d (GPX_PREC_F32 or GPX_PREC_BF16)", name, prec)
+
+long long conv_s1_workspace(int B, int Cin, int Cout, int H, int prec) {
+    return conv_shape_ok(B, Cin, Cout, H) && xyz_prec_ok(prec) ? 4LL * up64(conv_s1_ws_floats(B, Cin, Cout, H, prec)) : 0;
+}
+int conv_s1_forward_entry(const float* X, const float* Wt, int B, int Cin, int Cout, int H, float* Y, void* ws, long long ws_bytes,
+                          void* stream, int prec, const char* name) {
+    XYZ_PREC_REQUIRE(prec, name);
+    GP_REQUIRE(!ws || aligned256(ws), "%s: the workspace is not 256-byte aligned", name);
+    return conv_s1_forward(X, Wt, B, Cin, Cout, H, Y, (float*)ws, (long)(ws_bytes / 4), (hipStream_t)stream, prec, name);
+}
+int conv_s1_backward_entry(const float* dY, const float* X, const float* Wt, int B, int Cin, int Cout, int H, float* dX, float* dW, void* ws,
+                           long long ws_bytes, void* stream, int prec, const char* name) {
+    XYZ_PREC_REQUIRE(prec, name);
+    GP_REQUIRE(!ws || aligned256(ws), "%s: the workspace is not 256-byte aligned", name);
+    return conv_s1_backward(dY, X, Wt, B, Cin, Cout, H, dX, dW, (float*)ws, (long)(ws_bytes / 4), (hipStream_t)stream, prec, name);
+}
+
+long long deconv_workspace(int B, int Cin, int Cout, int H, int prec) {
+    return conv_shape_ok(B, Cin, Cout, 2L * H) && xyz_prec_ok(prec) ? 4LL * up64(deconv_ws_floats(B, Cin, Cout, H, prec)) : 0;
+}
+int deconv_forward_entry(const float* X, const float* Wt, int B, int Cin, int Cout, int H, float* Y, void* ws, long long ws_bytes,
+                         void* stream, int prec, const char* name) {
+    XYZ_PREC_REQUIRE(prec, name);
+    GP_REQUIRE(!ws || aligned256(ws), "%s: the workspace is not 256-byte aligned", name);
+    return deconv_forward(X, Wt, B, Cin, Cout, H, Y, (float*)ws, (long)(ws_bytes / 4), (hipStream_t)stream, prec, name);
+}
+int deconv_backward_entry(const float* dY, const float* X, const float* Wt, int B, int Cin, int Cout, int H, float* dX, float* dW, void* ws,
+                          long long ws_bytes, void* stream, int prec, const char* name) {
+    XYZ_PREC_REQUIRE(prec, name);
+    GP_REQUIRE(!ws || aligned256(ws), "%s: the workspace is not 256-byte aligned", name);
+    return deconv_backward(dY, X, Wt, B, Cin, Cout, H, dX, dW, (float*)ws, (long)(ws_bytes / 4), (hipStream_t)stream, prec, name);
+}
+
+long long head_forward_workspace(int B, int Cin, int H0, int prec) {
+    return head_shape_ok(B, Cin, H0) && xyz_prec_ok(prec) ? 4LL * head_fwd_ws_floats(B, Cin, H0, prec) : 0;
+}
+int head_forward_save(const float* feat, const gpx_xyz_params* w, int B, int Cin, int H0, const gpx_xyz_saved* sv, void* ws,
+                      long long ws_bytes, void* stream, int prec, const char* name) {
+    XYZ_PREC_REQUIRE(prec, name);
+    GP_REQUIRE(feat && params_complete(w) && saved_complete(sv), "%s: null pointer", name);
+    GP_REQUIRE(head_shape_ok(B, Cin, H0), "%s: bad shape B %d Cin %d H0 %d", name, B, Cin, H0);
+    GP_REQUIRE(!ws || aligned256(ws), "%s: the workspace is not 256-byte aligned", name);
+    GP_REQUIRE(ws_bytes / 4 >= head_fwd_ws_floats(B, Cin, H0, prec) && (ws || ws_bytes == 0), "%s: workspace too small", name);
+    hipStream_t s = (hipStream_t)stream;
+    float* f = (float*)ws;
+    const long wf = (long)(ws_bytes / 4);
+    GPH_TRY(deconv_forward(feat, w->deconv_w, B, Cin, FEAT, H0, sv->pre[0], f, wf, s, prec, name));
+    const float* in = nullptr;
+    for (int l = 0; l < LAYERS; ++l) {
+        const int H = MUL[l] * H0;
+        if (l == 3 || l == 5) {      // UpsamplingBilinear2d in front of the third and the fifth conv
+            float* up = sv->up[(l - 3) / 2];
+            GPH_TRY(upsample_forward(in, B, FEAT, H / 2, up, s, name));
+            in = up;
+        }
+        if (l > 0) GPH_TRY(conv_s1_forward(in, w->conv_w[l - 1], B, FEAT, FEAT, H, sv->pre[l], f, wf, s, prec, name));
+        GPH_TRY(gn_gelu_forward(sv->pre[l], w->gn_w[l], w->gn_b[l], B, FEAT, H * H, GROUPS, sv->act[l], sv->mean[l], sv->rstd[l], s, name));
+        in = sv->act[l];
+    }
+    return conv1x1_forward(in, w->out_w, w->out_b, B, FEAT, 3, 64 * H0 * H0, sv->coor, f, wf, s, name);
+}
+
+long long head_backward_workspace(int B, int Cin, int H0, int prec) {
+    return head_shape_ok(B, Cin, H0) && xyz_prec_ok(prec) ? 4LL * bwd_layout(B, Cin, H0, prec).total : 0;
+}
+int head_backward(const gpx_xyz_params* w, const gpx_xyz_saved* sv, const float* feat, const float* g_coor, int B, int Cin, int H0,
+                  const gpx_xyz_params* gr, float* g_feat, void* ws, long long ws_bytes, void* stream, int prec, const char* name) {
+    XYZ_PREC_REQUIRE(prec, name);
+    GP_REQUIRE(params_complete(w) && saved_complete(sv) && params_complete(gr) && feat && g_coor && g_feat, "%s: null pointer", name);
+    GP_REQUIRE(head_shape_ok(B, Cin, H0), "%s: bad shape B %d Cin %d H0 %d", name, B, Cin, H0);
+    const BwdLayout L = bwd_layout(B, Cin, H0, prec);
+    GP_REQUIRE(ws && aligned256(ws) && ws_bytes / 4 >= L.total, "%s: workspace missing, unaligned or too small", name);
+    hipStream_t s = (hipStream_t)stream;
+    float* f = (float*)ws;
+    float *da = f + L.p, *dc = f + L.q, *sc = f + L.scratch;      // da: gradient of a layer's output, dc: of its pre-norm map
+    const long sf = L.scratch_floats;
+    GPH_TRY(conv1x1_backward(g_coor, sv->act[LAYERS - 1], w->out_w, B, FEAT, 3, 64 * H0 * H0, da, gr->out_w, gr->out_b, sc, sf, s, name));
+    for (int l = LAYERS - 1; l >= 0; --l) {
+        const int H = MUL[l] * H0;
+        GPH_TRY(gn_gelu_backward(da, sv->pre[l], sv->mean[l], sv->rstd[l], w->gn_w[l], w->gn_b[l], B, FEAT, H * H, GROUPS, dc, gr->gn_w[l],
+                                 gr->gn_b[l], sc, sf, s, name));
+        if (l == 0) break;
+        const bool up = l == 3 || l == 5;
+        const float* in = up ? sv->up[(l - 3) / 2] : sv->act[l - 1];
+        GPH_TRY(conv_s1_backward(dc, in, w->conv_w[l - 1], B, FEAT, FEAT, H, da, gr->conv_w[l - 1], sc, sf, s, prec, name));
+        if (up) {      // back through the upsample: da (H) -> dc (H / 2) -> da for the layer below
+            GPH_TRY(upsample_backward(da, B, FEAT, H / 2, dc, s, name));
+            float* t = da;
+            da = dc;
+            dc = t;
+        }
+    }
+    return deconv_backward(dc, feat, w->deconv_w, B, Cin, FEAT, H0, g_feat, gr->deconv_w, sc, sf, s, prec, name);
+}
+
 }  // namespace
 
 extern "C" {
 
-long long gpx_conv3x3s1_workspace(int B, int Cin, int Cout, int H) {
-    return conv_shape_ok(B, Cin, Cout, H) ? 4LL * up64(conv_s1_ws_floats(B, Cin, Cout, H)) : 0;
-}
+long long gpx_conv3x3s1_workspace(int B, int Cin, int Cout, int H) { return conv_s1_workspace(B, Cin, Cout, H, GPX_PREC_F32); }
 
 int gpx_conv3x3s1_forward(const float* X, const float* Wt, int B, int Cin, int Cout, int H, float* Y, void* ws, long long ws_bytes,
                           void* stream) {
-    GP_REQUIRE(!ws || aligned256(ws), "gpx_conv3x3s1_forward: the workspace is not 256-byte aligned");
-    return conv_s1_forward(X, Wt, B, Cin, Cout, H, Y, (float*)ws, (long)(ws_bytes / 4), (hipStream_t)stream, "gpx_conv3x3s1_forward");
+    return conv_s1_forward_entry(X, Wt, B, Cin, Cout, H, Y, ws, ws_bytes, stream, GPX_PREC_F32, "gpx_conv3x3s1_forward");
 }
 
 int gpx_conv3x3s1_backward(const float* dY, const float* X, const float* Wt, int B, int Cin, int Cout, int H, float* dX, float* dW, void* ws,
                            long long ws_bytes, void* stream) {
-    GP_REQUIRE(!ws || aligned256(ws), "gpx_conv3x3s1_backward: the workspace is not 256-byte aligned");
-    return conv_s1_backward(dY, X, Wt, B, Cin, Cout, H, dX, dW, (float*)ws, (long)(ws_bytes / 4), (hipStream_t)stream,
-                            "gpx_conv3x3s1_backward");
+    return conv_s1_backward_entry(dY, X, Wt, B, Cin, Cout, H, dX, dW, ws, ws_bytes, stream, GPX_PREC_F32, "gpx_conv3x3s1_backward");
 }
 
-long long gpx_deconv3x3s2_workspace(int B, int Cin, int Cout, int H) {
-    return conv_shape_ok(B, Cin, Cout, 2L * H) ? 4LL * up64(deconv_ws_floats(B, Cin, Cout, H)) : 0;
-}
+long long gpx_deconv3x3s2_workspace(int B, int Cin, int Cout, int H) { return deconv_workspace(B, Cin, Cout, H, GPX_PREC_F32); }
 
 int gpx_deconv3x3s2_forward(const float* X, const float* Wt, int B, int Cin, int Cout, int H, float* Y, void* ws, long long ws_bytes,
                             void* stream) {
-    GP_REQUIRE(!ws || aligned256(ws), "gpx_deconv3x3s2_forward: the workspace is not 256-byte aligned");
-    return deconv_forward(X, Wt, B, Cin, Cout, H, Y, (float*)ws, (long)(ws_bytes / 4), (hipStream_t)stream, "gpx_deconv3x3s2_forward");
+    return deconv_forward_entry(X, Wt, B, Cin, Cout, H, Y, ws, ws_bytes, stream, GPX_PREC_F32, "gpx_deconv3x3s2_forward");
 }
 
 int gpx_deconv3x3s2_backward(const float* dY, const float* X, const float* Wt, int B, int Cin, int Cout, int H, float* dX, float* dW,
                              void* ws, long long ws_bytes, void* stream) {
-    GP_REQUIRE(!ws || aligned256(ws), "gpx_deconv3x3s2_backward: the workspace is not 256-byte aligned");
-    return deconv_backward(dY, X, Wt, B, Cin, Cout, H, dX, dW, (float*)ws, (long)(ws_bytes / 4), (hipStream_t)stream,
-                           "gpx_deconv3x3s2_backward");
+    return deconv_backward_entry(dY, X, Wt, B, Cin, Cout, H, dX, dW, ws, ws_bytes, stream, GPX_PREC_F32, "gpx_deconv3x3s2_backward");
 }
 
 long long gpx_gn_gelu_backward_workspace(int B, int C) { return B > 0 && C > 0 ? 4LL * gn_bwd_ws_floats(B, C) : 0; }
@@ -473,64 +556,57 @@ int gpx_conv1x1_backward(const float* dY, const float* X, const float* Wt, int B
                             "gpx_conv1x1_backward");
 }
 
-long long gpx_xyz_forward_workspace(int B, int Cin, int H0) { return head_shape_ok(B, Cin, H0) ? 4LL * head_fwd_ws_floats(B, Cin, H0) : 0; }
+long long gpx_xyz_forward_workspace(int B, int Cin, int H0) { return head_forward_workspace(B, Cin, H0, GPX_PREC_F32); }
 
 int gpx_xyz_forward_save(const float* feat, const gpx_xyz_params* w, int B, int Cin, int H0, const gpx_xyz_saved* sv, void* ws,
                          long long ws_bytes, void* stream) {
-    const char* name = "gpx_xyz_forward_save";
-    GP_REQUIRE(feat && params_complete(w) && saved_complete(sv), "%s: null pointer", name);
-    GP_REQUIRE(head_shape_ok(B, Cin, H0), "%s: bad shape B %d Cin %d H0 %d", name, B, Cin, H0);
-    GP_REQUIRE(!ws || aligned256(ws), "%s: the workspace is not 256-byte aligned", name);
-    GP_REQUIRE(ws_bytes / 4 >= head_fwd_ws_floats(B, Cin, H0) && (ws || ws_bytes == 0), "%s: workspace too small", name);
-    hipStream_t s = (hipStream_t)stream;
-    float* f = (float*)ws;
-    const long wf = (long)(ws_bytes / 4);
-    GPH_TRY(deconv_forward(feat, w->deconv_w, B, Cin, FEAT, H0, sv->pre[0], f, wf, s, name));
-    const float* in = nullptr;
-    for (int l = 0; l < LAYERS; ++l) {
-        const int H = MUL[l] * H0;
-        if (l == 3 || l == 5) {      // UpsamplingBilinear2d in front of the third and the fifth conv
-            float* up = sv->up[(l - 3) / 2];
-            GPH_TRY(upsample_forward(in, B, FEAT, H / 2, up, s, name));
-            in = up;
-        }
-        if (l > 0) GPH_TRY(conv_s1_forward(in, w->conv_w[l - 1], B, FEAT, FEAT, H, sv->pre[l], f, wf, s, name));
-        GPH_TRY(gn_gelu_forward(sv->pre[l], w->gn_w[l], w->gn_b[l], B, FEAT, H * H, GROUPS, sv->act[l], sv->mean[l], sv->rstd[l], s, name));
-        in = sv->act[l];
-    }
-    return conv1x1_forward(in, w->out_w, w->out_b, B, FEAT, 3, 64 * H0 * H0, sv->coor, f, wf, s, name);
+    return head_forward_save(feat, w, B, Cin, H0, sv, ws, ws_bytes, stream, GPX_PREC_F32, "gpx_xyz_forward_save");
 }
 
-long long gpx_xyz_backward_workspace(int B, int Cin, int H0) { return head_shape_ok(B, Cin, H0) ? 4LL * bwd_layout(B, Cin, H0).total : 0; }
+long long gpx_xyz_backward_workspace(int B, int Cin, int H0) { return head_backward_workspace(B, Cin, H0, GPX_PREC_F32); }
 
 int gpx_xyz_backward(const gpx_xyz_params* w, const gpx_xyz_saved* sv, const float* feat, const float* g_coor, int B, int Cin, int H0,
                      const gpx_xyz_params* gr, float* g_feat, void* ws, long long ws_bytes, void* stream) {
-    const char* name = "gpx_xyz_backward";
-    GP_REQUIRE(params_complete(w) && saved_complete(sv) && params_complete(gr) && feat && g_coor && g_feat, "%s: null pointer", name);
-    GP_REQUIRE(head_shape_ok(B, Cin, H0), "%s: bad shape B %d Cin %d H0 %d", name, B, Cin, H0);
-    const BwdLayout L = bwd_layout(B, Cin, H0);
-    GP_REQUIRE(ws && aligned256(ws) && ws_bytes / 4 >= L.total, "%s: workspace missing, unaligned or too small", name);
-    hipStream_t s = (hipStream_t)stream;
-    float* f = (float*)ws;
-    float *da = f + L.p, *dc = f + L.q, *sc = f + L.scratch;      // da: gradient of a layer's output, dc: of its pre-norm map
-    const long sf = L.scratch_floats;
-    GPH_TRY(conv1x1_backward(g_coor, sv->act[LAYERS - 1], w->out_w, B, FEAT, 3, 64 * H0 * H0, da, gr->out_w, gr->out_b, sc, sf, s, name));
-    for (int l = LAYERS - 1; l >= 0; --l) {
-        const int H = MUL[l] * H0;
-        GPH_TRY(gn_gelu_backward(da, sv->pre[l], sv->mean[l], sv->rstd[l], w->gn_w[l], w->gn_b[l], B, FEAT, H * H, GROUPS, dc, gr->gn_w[l],
-                                 gr->gn_b[l], sc, sf, s, name));
-        if (l == 0) break;
-        const bool up = l == 3 || l == 5;
-        const float* in = up ? sv->up[(l - 3) / 2] : sv->act[l - 1];
-        GPH_TRY(conv_s1_backward(dc, in, w->conv_w[l - 1], B, FEAT, FEAT, H, da, gr->conv_w[l - 1], sc, sf, s, name));
-        if (up) {      // back through the upsample: da (H) -> dc (H / 2) -> da for the layer below
-            GPH_TRY(upsample_backward(da, B, FEAT, H / 2, dc, s, name));
-            float* t = da;
-            da = dc;
-            dc = t;
-        }
-    }
-    return deconv_backward(dc, feat, w->deconv_w, B, Cin, FEAT, H0, g_feat, gr->deconv_w, sc, sf, s, name);
+    return head_backward(w, sv, feat, g_coor, B, Cin, H0, gr, g_feat, ws, ws_bytes, stream, GPX_PREC_F32, "gpx_xyz_backward");
+}
+
+/* ---- the precision-taking forms (include/givepose_xyzgrad_bf16.h) ---- */
+long long gpxm_conv3x3s1_workspace(int B, int Cin, int Cout, int H, int precision) { return conv_s1_workspace(B, Cin, Cout, H, precision); }
+
+int gpxm_conv3x3s1_forward(const float* X, const float* Wt, int B, int Cin, int Cout, int H, float* Y, void* ws, long long ws_bytes,
+                           void* stream, int precision) {
+    return conv_s1_forward_entry(X, Wt, B, Cin, Cout, H, Y, ws, ws_bytes, stream, precision, "gpxm_conv3x3s1_forward");
+}
+
+int gpxm_conv3x3s1_backward(const float* dY, const float* X, const float* Wt, int B, int Cin, int Cout, int H, float* dX, float* dW,
+                            void* ws, long long ws_bytes, void* stream, int precision) {
+    return conv_s1_backward_entry(dY, X, Wt, B, Cin, Cout, H, dX, dW, ws, ws_bytes, stream, precision, "gpxm_conv3x3s1_backward");
+}
+
+long long gpxm_deconv3x3s2_workspace(int B, int Cin, int Cout, int H, int precision) { return deconv_workspace(B, Cin, Cout, H, precision); }
+
+int gpxm_deconv3x3s2_forward(const float* X, const float* Wt, int B, int Cin, int Cout, int H, float* Y, void* ws, long long ws_bytes,
+                             void* stream, int precision) {
+    return deconv_forward_entry(X, Wt, B, Cin, Cout, H, Y, ws, ws_bytes, stream, precision, "gpxm_deconv3x3s2_forward");
+}
+
+int gpxm_deconv3x3s2_backward(const float* dY, const float* X, const float* Wt, int B, int Cin, int Cout, int H, float* dX, float* dW,
+                              void* ws, long long ws_bytes, void* stream, int precision) {
+    return deconv_backward_entry(dY, X, Wt, B, Cin, Cout, H, dX, dW, ws, ws_bytes, stream, precision, "gpxm_deconv3x3s2_backward");
+}
+
+long long gpxm_xyz_forward_workspace(int B, int Cin, int H0, int precision) { return head_forward_workspace(B, Cin, H0, precision); }
+
+int gpxm_xyz_forward_save(const float* feat, const gpx_xyz_params* w, int B, int Cin, int H0, const gpx_xyz_saved* sv, void* ws,
+                          long long ws_bytes, void* stream, int precision) {
+    return head_forward_save(feat, w, B, Cin, H0, sv, ws, ws_bytes, stream, precision, "gpxm_xyz_forward_save");
+}
+
+long long gpxm_xyz_backward_workspace(int B, int Cin, int H0, int precision) { return head_backward_workspace(B, Cin, H0, precision); }
+
+int gpxm_xyz_backward(const gpx_xyz_params* w, const gpx_xyz_saved* sv, const float* feat, const float* g_coor, int B, int Cin, int H0,
+                      const gpx_xyz_params* gr, float* g_feat, void* ws, long long ws_bytes, void* stream, int precision) {
+    return head_backward(w, sv, feat, g_coor, B, Cin, H0, gr, g_feat, ws, ws_bytes, stream, precision, "gpxm_xyz_backward");
 }
 
 }  // extern "C"

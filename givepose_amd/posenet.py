@@ -231,21 +231,36 @@ class PoseNet(nn.Module):
 
     # the precision of the backbone's recompute and backward (`backbone_backward`, and with it `head_grads_backbone` and `train_step`)
     _backward_precision = "fp32"
+    # the same for the two coordinate heads (`xyz_head_backward`, and with it `head_grads_xyz`, `head_grads_feat`, ... and `train_step`)
+    _xyz_backward_precision = "fp32"
 
     @property
     def backward_precision(self):
         """"fp32" (the default) or "bf16": see `set_backward_precision`."""
         return self._backward_precision
 
-    def set_backward_precision(self, mode):
+    @property
+    def xyz_backward_precision(self):
+        """"fp32" (the default) or "bf16": the `xyz_heads` argument of the last `set_backward_precision`."""
+        return self._xyz_backward_precision
+
+    def set_backward_precision(self, mode, xyz_heads="fp32"):
         """"fp32" (the default): the backbone's recompute and backward are the fp32 chains of the gpb_ family.
         "bf16": the six dense contractions of every ConvNeXt block multiply bf16-rounded operands and add in fp32, as
         torch.autocast(bfloat16) does elsewhere (givepose_amd.bb_grad, precision="bf16"; include/givepose_bbgrad_bf16.h); no loss scaling
         is needed.  Everything else in the chain -- the heads, the encoder, the loss, the optimiser, the forward -- is unchanged, and
-        switching back to "fp32" gives the bits of before.  Nothing is cached per mode: the switch costs nothing."""
+        switching back to "fp32" gives the bits of before.  Nothing is cached per mode: the switch costs nothing.
+        xyz_heads, "fp32" (the default) or "bf16", is the same switch for the two coordinate heads (`xyz_head_backward` of
+        xyz_nocs_head and xyz_deform_head): with "bf16" the 21 contractions of a head's 3x3 layers, in its recompute and in its backward,
+        take bf16-rounded operands (givepose_amd.xyz_grad, precision="bf16"; include/givepose_xyzgrad_bf16.h), the rest of the head stays
+        fp32.  Every call sets both: set_backward_precision("bf16") alone leaves the heads at their fp32 bits, and
+        set_backward_precision("fp32") is everything as before."""
         if mode not in ("fp32", "bf16"):
             raise ValueError(f"set_backward_precision: {mode!r}, expected 'fp32' or 'bf16'")
+        if xyz_heads not in ("fp32", "bf16"):
+            raise ValueError(f"set_backward_precision: xyz_heads {xyz_heads!r}, expected 'fp32' or 'bf16'")
         self._backward_precision = mode
+        self._xyz_backward_precision = xyz_heads
         return self
 
     def _pack_device(self, device):
@@ -1256,8 +1271,11 @@ class PoseNet(nn.Module):
             Parameter with one .grad; there are 23 distinct tensors --,
             "feat": (B,Cin,8,8), the gradient of the input feature, "outputs": {"coor": (B,3,64,64)} of the fp32 recompute};
         return_saved adds "saved", the saved activations (givepose_amd.xyz_grad.saved_shapes).
-        The weights are read at every call: a parameter updated in place between two calls is differentiated at its new value."""
+        The weights are read at every call: a parameter updated in place between two calls is differentiated at its new value.
+        Under set_backward_precision(..., xyz_heads="bf16") (`xyz_backward_precision`) the 3x3 layers' contractions of both passes take
+        bf16-rounded operands (fp32 sums); parameters, saved tensors and results stay fp32."""
         from . import xyz_grad
+        precision = self._xyz_backward_precision
         if head not in self._XYZ_HEADS:
             raise ValueError(f"xyz_head_backward: head {head!r}, expected one of {self._XYZ_HEADS}")
         dev = torch.device(device)
@@ -1268,8 +1286,8 @@ class PoseNet(nn.Module):
         if feat.dim() != 4 or feat.shape[1] != Cin or feat.shape[2] != feat.shape[3]:
             raise ValueError(f"xyz_head_backward: feat {tuple(feat.shape)}, expected (B,{Cin},H0,H0)")
         feat = feat.to(torch.float32).contiguous()
-        saved = xyz_grad.xyz_forward_save(feat, P)
-        grads, g_feat = xyz_grad.xyz_backward(P, saved, feat, torch.as_tensor(g_coor).to(dev))
+        saved = xyz_grad.xyz_forward_save(feat, P, precision=precision)
+        grads, g_feat = xyz_grad.xyz_backward(P, saved, feat, torch.as_tensor(g_coor).to(dev), precision=precision)
         pg = {f"{head}.{k}": v for k, v in grads.items()}
         for alias, k in xyz_grad.ALIASES.items():
             pg[f"{head}.{alias}"] = grads[k]

@@ -7,6 +7,10 @@ gradient lies under the index of its parameter and nothing has to be permuted ba
 
 `alloc(name, shape)` -- an optional hook every function takes -- supplies the output and workspace buffers (fp32, contiguous, on
 the device; workspaces 256-byte aligned); the default is torch.empty.  The tests use it to put sentinels around every buffer.
+
+`precision="fp32"` (the default) is the gpx_ entry points themselves.  `precision="bf16"` on the 3x3 convs, the transposed conv and
+the head (include/givepose_xyzgrad_bf16.h, gpxm_*) multiplies bf16-rounded operands and adds in fp32 in the 21 contractions of the
+3x3 layers; GroupNorm + GELU, the bilinear x2 and the 1x1 output conv stay fp32, and so does everything in memory.
 """
 import ctypes
 
@@ -82,6 +86,28 @@ def _saved_struct(saved, B, Cin, H0):
     return st
 
 
+PRECISIONS = {"fp32": _lib.GPX_PREC_F32, "bf16": _lib.GPX_PREC_BF16}
+
+
+def _prec(precision):
+    """The GPX_PREC_* value of "fp32" or "bf16" (include/givepose_xyzgrad_bf16.h)."""
+    if not isinstance(precision, str) or precision not in PRECISIONS:
+        raise ValueError(f"precision: {precision!r}, expected 'fp32' or 'bf16'")
+    return PRECISIONS[precision]
+
+
+def _entry(L, stem, prec):
+    """(function, its name, trailing arguments) of gpx_<stem> in a precision: "fp32" is the gpx_ entry point itself."""
+    if prec == _lib.GPX_PREC_F32:
+        return getattr(L, "gpx_" + stem), "gpx_" + stem, ()
+    return getattr(L, "gpxm_" + stem), "gpxm_" + stem, (prec,)
+
+
+def _query(L, stem, prec, *args):
+    fn, _, tail = _entry(L, stem, prec)
+    return fn(*args, *tail)
+
+
 def _call(dev, fn, name, *args):
     with torch.cuda.device(dev):
         _lib.check(fn(*args), name)
@@ -98,61 +124,70 @@ def _conv_args(X, W, transposed):
 
 
 @torch.no_grad()
-def conv3x3s1_forward(X, W, alloc=None):
-    """F.conv2d(X, W, padding=1) without bias in fp32: X (B,Cin,H,H), W (Cout,Cin,3,3) -> (B,Cout,H,H)."""
+def conv3x3s1_forward(X, W, alloc=None, precision="fp32"):
+    """F.conv2d(X, W, padding=1) without bias: X (B,Cin,H,H), W (Cout,Cin,3,3) -> (B,Cout,H,H), fp32.
+    precision="bf16": the contraction multiplies bf16-rounded operands and adds in fp32 (gpxm_conv3x3s1_forward)."""
+    prec = _prec(precision)
     dev, B, Cin, Cout, H, X, W = _conv_args(X, W, False)
     alloc = alloc or _default_alloc(dev)
     L = _lib.load()
     Y = alloc("Y", (B, Cout, H, H))
-    nbytes = L.gpx_conv3x3s1_workspace(B, Cin, Cout, H)
+    nbytes = _query(L, "conv3x3s1_workspace", prec, B, Cin, Cout, H)
     ws = _ws(alloc, nbytes)
-    _call(dev, L.gpx_conv3x3s1_forward, "gpx_conv3x3s1_forward", X.data_ptr(), W.data_ptr(), B, Cin, Cout, H, Y.data_ptr(), ws.data_ptr(),
-          nbytes, _stream(dev))
+    fn, name, tail = _entry(L, "conv3x3s1_forward", prec)
+    _call(dev, fn, name, X.data_ptr(), W.data_ptr(), B, Cin, Cout, H, Y.data_ptr(), ws.data_ptr(), nbytes, _stream(dev), *tail)
     return Y
 
 
 @torch.no_grad()
-def conv3x3s1_backward(dY, X, W, alloc=None):
-    """Backward of F.conv2d(X, W, padding=1) without bias: dY (B,Cout,H,H) -> {"dX": (B,Cin,H,H), "dW": (Cout,Cin,3,3)}."""
+def conv3x3s1_backward(dY, X, W, alloc=None, precision="fp32"):
+    """Backward of F.conv2d(X, W, padding=1) without bias: dY (B,Cout,H,H) -> {"dX": (B,Cin,H,H), "dW": (Cout,Cin,3,3)}.
+    precision="bf16": both contractions multiply bf16-rounded operands and add in fp32 (gpxm_conv3x3s1_backward)."""
+    prec = _prec(precision)
     dev, B, Cin, Cout, H, X, W = _conv_args(X, W, False)
     dY = _f32(dY, dev, (B, Cout, H, H), "dY")
     alloc = alloc or _default_alloc(dev)
     L = _lib.load()
     dX, dW = alloc("dX", (B, Cin, H, H)), alloc("dW", (Cout, Cin, 3, 3))
-    nbytes = L.gpx_conv3x3s1_workspace(B, Cin, Cout, H)
+    nbytes = _query(L, "conv3x3s1_workspace", prec, B, Cin, Cout, H)
     ws = _ws(alloc, nbytes)
-    _call(dev, L.gpx_conv3x3s1_backward, "gpx_conv3x3s1_backward", dY.data_ptr(), X.data_ptr(), W.data_ptr(), B, Cin, Cout, H, dX.data_ptr(),
-          dW.data_ptr(), ws.data_ptr(), nbytes, _stream(dev))
+    fn, name, tail = _entry(L, "conv3x3s1_backward", prec)
+    _call(dev, fn, name, dY.data_ptr(), X.data_ptr(), W.data_ptr(), B, Cin, Cout, H, dX.data_ptr(), dW.data_ptr(), ws.data_ptr(), nbytes,
+          _stream(dev), *tail)
     return {"dX": dX, "dW": dW}
 
 
 @torch.no_grad()
-def deconv3x3s2_forward(X, W, alloc=None):
-    """F.conv_transpose2d(X, W, stride=2, padding=1, output_padding=1) without bias in fp32: X (B,Cin,H,H), W (Cin,Cout,3,3)
-    -> (B,Cout,2H,2H)."""
+def deconv3x3s2_forward(X, W, alloc=None, precision="fp32"):
+    """F.conv_transpose2d(X, W, stride=2, padding=1, output_padding=1) without bias: X (B,Cin,H,H), W (Cin,Cout,3,3)
+    -> (B,Cout,2H,2H), fp32.  precision="bf16": bf16-rounded operands, fp32 sums (gpxm_deconv3x3s2_forward)."""
+    prec = _prec(precision)
     dev, B, Cin, Cout, H, X, W = _conv_args(X, W, True)
     alloc = alloc or _default_alloc(dev)
     L = _lib.load()
     Y = alloc("Y", (B, Cout, 2 * H, 2 * H))
-    nbytes = L.gpx_deconv3x3s2_workspace(B, Cin, Cout, H)
+    nbytes = _query(L, "deconv3x3s2_workspace", prec, B, Cin, Cout, H)
     ws = _ws(alloc, nbytes)
-    _call(dev, L.gpx_deconv3x3s2_forward, "gpx_deconv3x3s2_forward", X.data_ptr(), W.data_ptr(), B, Cin, Cout, H, Y.data_ptr(), ws.data_ptr(),
-          nbytes, _stream(dev))
+    fn, name, tail = _entry(L, "deconv3x3s2_forward", prec)
+    _call(dev, fn, name, X.data_ptr(), W.data_ptr(), B, Cin, Cout, H, Y.data_ptr(), ws.data_ptr(), nbytes, _stream(dev), *tail)
     return Y
 
 
 @torch.no_grad()
-def deconv3x3s2_backward(dY, X, W, alloc=None):
-    """Backward of the transposed conv: dY (B,Cout,2H,2H) -> {"dX": (B,Cin,H,H), "dW": (Cin,Cout,3,3)}."""
+def deconv3x3s2_backward(dY, X, W, alloc=None, precision="fp32"):
+    """Backward of the transposed conv: dY (B,Cout,2H,2H) -> {"dX": (B,Cin,H,H), "dW": (Cin,Cout,3,3)}.
+    precision="bf16": both contractions multiply bf16-rounded operands and add in fp32 (gpxm_deconv3x3s2_backward)."""
+    prec = _prec(precision)
     dev, B, Cin, Cout, H, X, W = _conv_args(X, W, True)
     dY = _f32(dY, dev, (B, Cout, 2 * H, 2 * H), "dY")
     alloc = alloc or _default_alloc(dev)
     L = _lib.load()
     dX, dW = alloc("dX", (B, Cin, H, H)), alloc("dW", (Cin, Cout, 3, 3))
-    nbytes = L.gpx_deconv3x3s2_workspace(B, Cin, Cout, H)
+    nbytes = _query(L, "deconv3x3s2_workspace", prec, B, Cin, Cout, H)
     ws = _ws(alloc, nbytes)
-    _call(dev, L.gpx_deconv3x3s2_backward, "gpx_deconv3x3s2_backward", dY.data_ptr(), X.data_ptr(), W.data_ptr(), B, Cin, Cout, H,
-          dX.data_ptr(), dW.data_ptr(), ws.data_ptr(), nbytes, _stream(dev))
+    fn, name, tail = _entry(L, "deconv3x3s2_backward", prec)
+    _call(dev, fn, name, dY.data_ptr(), X.data_ptr(), W.data_ptr(), B, Cin, Cout, H, dX.data_ptr(), dW.data_ptr(), ws.data_ptr(), nbytes,
+          _stream(dev), *tail)
     return {"dX": dX, "dW": dW}
 
 
@@ -226,9 +261,12 @@ def conv1x1_backward(dY, X, W, alloc=None):
 
 # ------------------------------------------------------------------------------------------------ the head
 @torch.no_grad()
-def xyz_forward_save(feat, params, alloc=None):
+def xyz_forward_save(feat, params, alloc=None, precision="fp32"):
     """TopDownXyzHead.forward in fp32 (gpx_xyz_forward_save): feat (B,Cin,H0,H0), params {name: fp32 device tensor} over PARAM_KEYS
-    -> the saved activations (saved_shapes); saved["coor"] (B,3,8 H0,8 H0) is the head's result."""
+    -> the saved activations (saved_shapes); saved["coor"] (B,3,8 H0,8 H0) is the head's result.
+    precision="bf16": the transposed conv and the six 3x3 convs multiply bf16-rounded operands and add in fp32
+    (gpxm_xyz_forward_save); what is saved has the same shapes and dtypes."""
+    prec = _prec(precision)
     dev = _dev(feat)
     B, Cin, H0 = feat.shape[:3]
     if B == 0:
@@ -238,18 +276,21 @@ def xyz_forward_save(feat, params, alloc=None):
     saved = {k: [alloc(f"{k}{i}", s) for i, s in enumerate(v)] if isinstance(v, list) else alloc(k, v)
              for k, v in saved_shapes(B, Cin, H0).items()}
     L = _lib.load()
-    nbytes = L.gpx_xyz_forward_workspace(B, Cin, H0)
+    nbytes = _query(L, "xyz_forward_workspace", prec, B, Cin, H0)
     ws = _ws(alloc, nbytes)
     pw, sv = _params_struct(params, Cin, "params"), _saved_struct(saved, B, Cin, H0)
-    _call(dev, L.gpx_xyz_forward_save, "gpx_xyz_forward_save", feat.data_ptr(), ctypes.byref(pw), B, Cin, H0, ctypes.byref(sv), ws.data_ptr(),
-          nbytes, _stream(dev))
+    fn, name, tail = _entry(L, "xyz_forward_save", prec)
+    _call(dev, fn, name, feat.data_ptr(), ctypes.byref(pw), B, Cin, H0, ctypes.byref(sv), ws.data_ptr(), nbytes, _stream(dev), *tail)
     return saved
 
 
 @torch.no_grad()
-def xyz_backward(params, saved, feat, g_coor, alloc=None):
+def xyz_backward(params, saved, feat, g_coor, alloc=None, precision="fp32"):
     """gpx_xyz_backward: from d coor (B,3,8 H0,8 H0), the head's input feat and what xyz_forward_save returned for it (and the same
-    params) -> ({name: gradient} over PARAM_KEYS, d feat (B,Cin,H0,H0))."""
+    params) -> ({name: gradient} over PARAM_KEYS, d feat (B,Cin,H0,H0)).
+    precision="bf16": dX and dW of the transposed conv and of the six 3x3 convs multiply bf16-rounded operands and add in fp32
+    (gpxm_xyz_backward); `saved` may come from a forward of either precision."""
+    prec = _prec(precision)
     dev = _dev(feat)
     B, Cin, H0 = feat.shape[:3]
     feat = _f32(feat, dev, (B, Cin, H0, H0), "feat")
@@ -258,9 +299,10 @@ def xyz_backward(params, saved, feat, g_coor, alloc=None):
     grads = {k: alloc(k, s) for k, s in param_shapes(Cin).items()}
     g_feat = alloc("feat", (B, Cin, H0, H0))
     L = _lib.load()
-    nbytes = L.gpx_xyz_backward_workspace(B, Cin, H0)
+    nbytes = _query(L, "xyz_backward_workspace", prec, B, Cin, H0)
     ws = _ws(alloc, nbytes)
     pw, sv, pg = _params_struct(params, Cin, "params"), _saved_struct(saved, B, Cin, H0), _params_struct(grads, Cin, "grads")
-    _call(dev, L.gpx_xyz_backward, "gpx_xyz_backward", ctypes.byref(pw), ctypes.byref(sv), feat.data_ptr(), g_coor.data_ptr(), B, Cin, H0,
-          ctypes.byref(pg), g_feat.data_ptr(), ws.data_ptr(), nbytes, _stream(dev))
+    fn, name, tail = _entry(L, "xyz_backward", prec)
+    _call(dev, fn, name, ctypes.byref(pw), ctypes.byref(sv), feat.data_ptr(), g_coor.data_ptr(), B, Cin, H0, ctypes.byref(pg),
+          g_feat.data_ptr(), ws.data_ptr(), nbytes, _stream(dev), *tail)
     return grads, g_feat
