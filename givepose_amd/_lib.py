@@ -239,6 +239,16 @@ ENCGRAD_PROTOTYPES = {
 }
 GPE_FEAT, GPE_DCN_GROUPS, GPE_DCN_CHANNELS, GPE_TAPS, GPE_GN_GROUPS, GPE_LAYERS = 256, 4, 64, 9, 32, 3
 
+# its forms with a selectable d xp scatter (include/givepose_encgrad_ordered.h, prefix gpeo_; tests/test_enc_ordered_cpu.py checks both
+# ways): a trailing `scatter`, and for the core a workspace
+GPE_SCATTER_ATOMIC, GPE_SCATTER_ORDERED = 0, 1
+ENCGRAD_ORDERED_PROTOTYPES = {
+    "gpeo_dcnv3_core_backward_workspace": ([c_int] * 4, c_longlong),
+    "gpeo_dcnv3_core_backward": (ENCGRAD_PROTOTYPES["gpe_dcnv3_core_backward"][0] + [c_int, _P, c_longlong], c_int),
+    "gpeo_map_encoder_backward_workspace": ([c_int] * 3, c_longlong),
+    "gpeo_map_encoder_backward": (ENCGRAD_PROTOTYPES["gpe_map_encoder_backward"][0] + [c_int], c_int),
+}
+
 
 # the backbone backward family (include/givepose_bbgrad.h, prefix gpb_; tests/test_bb_backward_cpu.py checks both ways)
 class BbBlockParams(Structure):       # gpb_block_params: the 9 tensors of one ConvNeXt block in state_dict order
@@ -391,6 +401,7 @@ def load():
     for name, (argtypes, restype) in (list(PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items())
                                       + list(GRAD_PROTOTYPES.items()) + list(HEADGRAD_PROTOTYPES.items())
                                       + list(XYZGRAD_PROTOTYPES.items()) + list(XYZGRAD_BF16_PROTOTYPES.items()) + list(ENCGRAD_PROTOTYPES.items())
+                                      + list(ENCGRAD_ORDERED_PROTOTYPES.items())
                                       + list(BBGRAD_PROTOTYPES.items()) + list(BBGRAD_BF16_PROTOTYPES.items()) + list(OPTIM_PROTOTYPES.items())
                                       + list(SIZEGRAD_PROTOTYPES.items()) + list(ACCUM_PROTOTYPES.items())
                                       + list(REPACK_PROTOTYPES.items()) + list(TRAINDATA_PROTOTYPES.items())):

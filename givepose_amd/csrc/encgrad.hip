@@ -6,9 +6,13 @@
 // views, not kernels.  What is not a contraction: the ordered row sums (colsum), the depth-wise 3x3 + LayerNorm + GELU on a flat
 // prefix, the DCNv3 core of this geometry (one wavefront per (row, group), a lane per channel) and GroupNorm + ReLU.
 //
+// d xp of the core is scattered with fp32 atomics here, or left to the ordered sum of encscatter.hip (givepose_encgrad_ordered.h, gpeo_*:
+// the gpe_ entry points are the gpeo_ ones at GPE_SCATTER_ATOMIC).
+//
 // The size queries and the entry points run the same host code: a Scratch in `dry` mode only records what a run would take.
 #include "grad_gemm.hpp"
-#include "../../include/givepose_encgrad.h"
+#include "../../include/givepose_encgrad_ordered.h"
+#include "encscatter.hpp"
 
 namespace {
 
@@ -361,6 +365,8 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// SCATTER false (GPE_SCATTER_ORDERED): d xp is left to encscatter.hip, everything else is the same code
+template <bool SCATTER>
 __global__ __launch_bounds__(WG) void core_backward_kernel(const float* __restrict__ xp, const float* __restrict__ offset,
                                                            const float* __restrict__ mask, const float* __restrict__ dy, int H, int W,
                                                            int Ho, int Wo, long rows, float* dxp, float* __restrict__ doffset,
@@ -388,10 +394,10 @@ __global__ __launch_bounds__(WG) void core_backward_kernel(const float* __restri
         const float tg = top_grad * mq[q];
         const float w1 = t.hh * t.hw, w2 = t.hh * t.lw, w3 = t.lh * t.hw, w4 = t.lh * t.lw;
         float v1 = 0.0f, v2 = 0.0f, v3 = 0.0f, v4 = 0.0f, ghc = 0.0f, gwc = 0.0f;
-        if (t.o1) { v1 = im[t.a1]; ghc -= t.hw * v1; gwc -= t.hh * v1; atomicAdd(gim + t.a1, w1 * tg); }
-        if (t.o2) { v2 = im[t.a1 + ws_]; ghc -= t.lw * v2; gwc += t.hh * v2; atomicAdd(gim + t.a1 + ws_, w2 * tg); }
-        if (t.o3) { v3 = im[t.a1 + hs_]; ghc += t.hw * v3; gwc -= t.lh * v3; atomicAdd(gim + t.a1 + hs_, w3 * tg); }
-        if (t.o4) { v4 = im[t.a1 + hs_ + ws_]; ghc += t.lw * v4; gwc += t.lh * v4; atomicAdd(gim + t.a1 + hs_ + ws_, w4 * tg); }
+        if (t.o1) { v1 = im[t.a1]; ghc -= t.hw * v1; gwc -= t.hh * v1; if (SCATTER) atomicAdd(gim + t.a1, w1 * tg); }
+        if (t.o2) { v2 = im[t.a1 + ws_]; ghc -= t.lw * v2; gwc += t.hh * v2; if (SCATTER) atomicAdd(gim + t.a1 + ws_, w2 * tg); }
+        if (t.o3) { v3 = im[t.a1 + hs_]; ghc += t.hw * v3; gwc -= t.lh * v3; if (SCATTER) atomicAdd(gim + t.a1 + hs_, w3 * tg); }
+        if (t.o4) { v4 = im[t.a1 + hs_ + ws_]; ghc += t.lw * v4; gwc += t.lh * v4; if (SCATTER) atomicAdd(gim + t.a1 + hs_ + ws_, w4 * tg); }
         gm[q] = wave_sum(top_grad * (w1 * v1 + w2 * v2 + w3 * v3 + w4 * v4));
         const float gw = wave_sum(gwc * tg), gh = wave_sum(ghc * tg);
         if (lane == 0) {      // the one writer of this (row, group, tap); zeros for a tap outside the image
@@ -419,13 +425,26 @@ int core_forward(const float* xp, const float* offset, const float* logits, int 
     return 0;
 }
 
+bool scatter_ok(int scatter) { return scatter == GPE_SCATTER_ATOMIC || scatter == GPE_SCATTER_ORDERED; }
+
+long index_floats(int scatter, long N, long H, long W) {
+    return scatter == GPE_SCATTER_ORDERED ? encscatter::ordered_dxp_ws_floats(N, H, W) : 0;
+}
+
+// index: index_floats() words of the caller's scratch (the ordered mode's inverted index), null in the atomic mode
 int core_backward(const float* xp, const float* offset, const float* mask, const float* dy, int N, int H, int W, float* dxp, float* doffset,
-                  float* dlogits, hipStream_t s, const char* name) {
+                  float* dlogits, int scatter, float* index, hipStream_t s, const char* name) {
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     const long rows = (long)N * Ho * Wo;
+    if (scatter == GPE_SCATTER_ORDERED) {
+        hipLaunchKernelGGL(core_backward_kernel<false>, dim3(cdiv(rows * DG, 4)), dim3(WG), 0, s, xp, offset, mask, dy, H, W, Ho, Wo, rows, dxp,
+                           doffset, dlogits);
+        GPH_CHECK(name);
+        return encscatter::ordered_dxp(offset, mask, dy, N, H, W, dxp, index, index_floats(scatter, N, H, W), s, name);
+    }
     const hipError_t e = hipMemsetAsync(dxp, 0, (size_t)N * H * W * FEAT * sizeof(float), s);
     if (e != hipSuccess) return gp_fail(GP_ERR_RUNTIME, "%s: hipMemsetAsync: %s", name, hipGetErrorString(e));
-    hipLaunchKernelGGL(core_backward_kernel, dim3(cdiv(rows * DG, 4)), dim3(WG), 0, s, xp, offset, mask, dy, H, W, Ho, Wo, rows, dxp, doffset,
+    hipLaunchKernelGGL(core_backward_kernel<true>, dim3(cdiv(rows * DG, 4)), dim3(WG), 0, s, xp, offset, mask, dy, H, W, Ho, Wo, rows, dxp, doffset,
                        dlogits);
     GPH_CHECK(name);
     return 0;
@@ -615,7 +634,7 @@ int enc_forward(const float* coor, const gpe_enc_params* w, int N, int R, const 
 }
 
 int enc_backward(const gpe_enc_params* w, const gpe_enc_saved* sv, const float* coor, const float* g_feat, int N, int R,
-                 const gpe_enc_params* gr, float* g_coor, Scratch& sc, hipStream_t s, const char* name) {
+                 const gpe_enc_params* gr, float* g_coor, int scatter, Scratch& sc, hipStream_t s, const char* name) {
     // the gradient of layer l's input map is layer l - 1's upstream gradient: two buffers that live across layers
     float* dmap[LAYERS] = {g_coor, sc.take((long)N * FEAT * (R / 2) * (R / 2)), sc.take((long)N * FEAT * (R / 4) * (R / 4))};
     const float* da = g_feat;
@@ -632,13 +651,14 @@ int enc_backward(const gpe_enc_params* w, const gpe_enc_saved* sv, const float* 
         float* dml = sc.take(np * MASKW);
         float* dx1 = sc.take(np * FEAT);
         float* dx = sc.take(rows * FEAT);
+        float* index = scatter == GPE_SCATTER_ORDERED ? sc.take(index_floats(scatter, N, H, H)) : nullptr;
         GPH_TRY(gn_relu_backward(da, v.pre, v.gn_mean, v.gn_rstd, p.gn_w, p.gn_b, N, FEAT, Ho * Ho, GNG, dpre, g.gn_w, g.gn_b, sc, s, name));
         // output_proj on the rows of the NCHW gradient
         const Nchw dout{dpre, FEAT, Ho * Ho};
         GPH_TRY(gemm_s(dout, MatRow{p.out_w, FEAT}, EpRow{dy, FEAT, nullptr, 0, 0}, np, FEAT, FEAT, sc, s, name));
         GPH_TRY(gemm_s(Tr<Nchw>{dout}, MatRow{v.y, FEAT}, EpRow{g.out_w, FEAT, nullptr, 0, 0}, FEAT, FEAT, np, sc, s, name));
         GPH_TRY(colsum_s(dout, np, FEAT, g.out_b, sc, s, name));
-        if (!sc.dry) GPH_TRY(core_backward(v.xp, v.offset, v.mask, dy, N, H, H, dxp, doff, dml, s, name));
+        if (!sc.dry) GPH_TRY(core_backward(v.xp, v.offset, v.mask, dy, N, H, H, dxp, doff, dml, scatter, index, s, name));
         // the offset / mask branch, prefix rows only: d x1 is the sum of the two Linears' parts, in this order
         GPH_TRY(linear_backward(doff, v.x1, p.off_w, np, FEAT, OFFW, dx1, 0, g.off_w, g.off_b, sc, s, name));
         GPH_TRY(linear_backward(dml, v.x1, p.mask_w, np, FEAT, MASKW, dx1, 1, g.mask_w, g.mask_b, sc, s, name));
@@ -733,12 +753,27 @@ int gpe_dcnv3_core_forward(const float* xp, const float* offset, const float* ma
     return core_forward(xp, offset, mask_logits, N, H, W, mask, y, (hipStream_t)stream, name);
 }
 
-int gpe_dcnv3_core_backward(const float* xp, const float* offset, const float* mask, const float* dy, int N, int H, int W, float* dxp,
-                            float* doffset, float* dmask_logits, void* stream) {
-    const char* name = "gpe_dcnv3_core_backward";
+long long gpeo_dcnv3_core_backward_workspace(int N, int H, int W, int scatter) {
+    if (!core_ok(N, H, W) || !scatter_ok(scatter)) return 0;
+    return 4LL * up64(index_floats(scatter, N, H, W));
+}
+
+int gpeo_dcnv3_core_backward(const float* xp, const float* offset, const float* mask, const float* dy, int N, int H, int W, float* dxp,
+                             float* doffset, float* dmask_logits, void* stream, int scatter, void* ws, long long ws_bytes) {
+    const char* name = scatter == GPE_SCATTER_ATOMIC ? "gpe_dcnv3_core_backward" : "gpeo_dcnv3_core_backward";
+    GP_REQUIRE(scatter_ok(scatter), "%s: unknown scatter mode %d (GPE_SCATTER_ATOMIC 0, GPE_SCATTER_ORDERED 1)", name, scatter);
     GP_REQUIRE(xp && offset && mask && dy && dxp && doffset && dmask_logits, "%s: null pointer", name);
     GP_REQUIRE(core_ok(N, H, W), "%s: bad shape N %d H %d W %d", name, N, H, W);
-    return core_backward(xp, offset, mask, dy, N, H, W, dxp, doffset, dmask_logits, (hipStream_t)stream, name);
+    const long long need = gpeo_dcnv3_core_backward_workspace(N, H, W, scatter);
+    GP_REQUIRE(need == 0 || (ws && aligned256(ws) && ws_bytes >= need), "%s: workspace missing, unaligned or too small (%lld bytes, %lld needed)",
+               name, ws_bytes, need);
+    return core_backward(xp, offset, mask, dy, N, H, W, dxp, doffset, dmask_logits, scatter, need ? (float*)ws : nullptr, (hipStream_t)stream,
+                         name);
+}
+
+int gpe_dcnv3_core_backward(const float* xp, const float* offset, const float* mask, const float* dy, int N, int H, int W, float* dxp,
+                            float* doffset, float* dmask_logits, void* stream) {
+    return gpeo_dcnv3_core_backward(xp, offset, mask, dy, N, H, W, dxp, doffset, dmask_logits, stream, GPE_SCATTER_ATOMIC, nullptr, 0);
 }
 
 int gpe_gn_relu_forward(const float* x, const float* gamma, const float* beta, int B, int C, int HW, int G, float* out, float* mean,
@@ -796,21 +831,30 @@ int gpe_map_encoder_forward_save(const float* coor, const gpe_enc_params* w, int
     return enc_forward(coor, w, N, R, saved, sc, (hipStream_t)stream, name);
 }
 
-long long gpe_map_encoder_backward_workspace(int N, int R) {
-    if (!enc_ok(N, R)) return 0;
+long long gpeo_map_encoder_backward_workspace(int N, int R, int scatter) {
+    if (!enc_ok(N, R) || !scatter_ok(scatter)) return 0;
     Scratch d(nullptr, 0, true);
-    enc_backward(&NO_PARAMS, &NO_SAVED, nullptr, nullptr, N, R, &NO_PARAMS, nullptr, d, nullptr, "");
+    enc_backward(&NO_PARAMS, &NO_SAVED, nullptr, nullptr, N, R, &NO_PARAMS, nullptr, scatter, d, nullptr, "");
     return 4LL * d.need;
 }
 
-int gpe_map_encoder_backward(const gpe_enc_params* w, const gpe_enc_saved* saved, const float* coor, const float* g_feat, int N, int R,
-                             const gpe_enc_params* grads, float* g_coor, void* ws, long long ws_bytes, void* stream) {
-    const char* name = "gpe_map_encoder_backward";
+int gpeo_map_encoder_backward(const gpe_enc_params* w, const gpe_enc_saved* saved, const float* coor, const float* g_feat, int N, int R,
+                              const gpe_enc_params* grads, float* g_coor, void* ws, long long ws_bytes, void* stream, int scatter) {
+    const char* name = scatter == GPE_SCATTER_ATOMIC ? "gpe_map_encoder_backward" : "gpeo_map_encoder_backward";
+    GP_REQUIRE(scatter_ok(scatter), "%s: unknown scatter mode %d (GPE_SCATTER_ATOMIC 0, GPE_SCATTER_ORDERED 1)", name, scatter);
     GP_REQUIRE(params_complete(w) && saved_complete(saved) && params_complete(grads) && coor && g_feat && g_coor, "%s: null pointer", name);
     GP_REQUIRE(enc_ok(N, R), "%s: bad shape N %d R %d", name, N, R);
-    GP_REQUIRE(ws && aligned256(ws) && ws_bytes >= gpe_map_encoder_backward_workspace(N, R), "%s: workspace missing, unaligned or too small", name);
+    GP_REQUIRE(ws && aligned256(ws) && ws_bytes >= gpeo_map_encoder_backward_workspace(N, R, scatter),
+               "%s: workspace missing, unaligned or too small", name);
     Scratch sc(ws, ws_bytes, false);
-    return enc_backward(w, saved, coor, g_feat, N, R, grads, g_coor, sc, (hipStream_t)stream, name);
+    return enc_backward(w, saved, coor, g_feat, N, R, grads, g_coor, scatter, sc, (hipStream_t)stream, name);
+}
+
+long long gpe_map_encoder_backward_workspace(int N, int R) { return gpeo_map_encoder_backward_workspace(N, R, GPE_SCATTER_ATOMIC); }
+
+int gpe_map_encoder_backward(const gpe_enc_params* w, const gpe_enc_saved* saved, const float* coor, const float* g_feat, int N, int R,
+                             const gpe_enc_params* grads, float* g_coor, void* ws, long long ws_bytes, void* stream) {
+    return gpeo_map_encoder_backward(w, saved, coor, g_feat, N, R, grads, g_coor, ws, ws_bytes, stream, GPE_SCATTER_ATOMIC);
 }
 
 }  // extern "C"

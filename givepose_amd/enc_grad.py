@@ -9,7 +9,9 @@ A coupling batch is the set of crops whose DCNv3 layers share one flat offset / 
 sizes of the forward that ran (None: one batch).  The batches are run one after the other and their parameter gradients are added
 in batch order.
 
-d xp is scattered with fp32 atomics: results are repeatable to rounding, not bit for bit, except where the header says so.
+d xp is scattered with fp32 atomics by default (`scatter="atomic"`): results are repeatable to rounding, not bit for bit, except
+where the header says so.  `scatter="ordered"` (include/givepose_encgrad_ordered.h, gpeo_*) adds the same terms per element in
+ascending order of their source id, without any floating-point atomic: two calls give equal bits in every output.
 
 `alloc(name, shape)` -- an optional hook every function takes -- supplies the output and workspace buffers (fp32, contiguous, on
 the device; workspaces 256-byte aligned); the default is torch.empty.  The tests use it to put sentinels around every buffer.
@@ -31,6 +33,16 @@ SAVED_KEYS = _lib.EncLayerSaved.FIELDS
 # of the last layer, what no scatter feeds (equal bits between runs)
 ATOMIC_FREE_KEYS = [f"features.6.dcnv3.{m}.{p}" for m in ("dw_conv.0", "dw_conv.1.1", "offset", "mask", "output_proj") for p in ("weight", "bias")] \
     + ["features.7.weight", "features.7.bias"]
+# with scatter="ordered" no floating-point atomic feeds anything: all 48 gradients and d coor are equal bits between runs
+ORDERED_FREE_KEYS = PARAM_KEYS
+SCATTER_MODES = {"atomic": _lib.GPE_SCATTER_ATOMIC, "ordered": _lib.GPE_SCATTER_ORDERED}
+
+
+def scatter_mode(scatter):
+    """"atomic" / "ordered" -> GPE_SCATTER_*; anything else raises ValueError naming the value."""
+    if not isinstance(scatter, str) or scatter not in SCATTER_MODES:
+        raise ValueError(f"scatter {scatter!r}: expected one of {tuple(SCATTER_MODES)}")
+    return SCATTER_MODES[scatter]
 
 
 def param_shapes():
@@ -202,9 +214,12 @@ def dcnv3_core_forward(xp, offset, mask_logits, alloc=None):
 
 
 @torch.no_grad()
-def dcnv3_core_backward(xp, offset, mask, dy, alloc=None):
+def dcnv3_core_backward(xp, offset, mask, dy, alloc=None, scatter="atomic"):
     """Backward of dcnv3_core_forward given its probabilities `mask`: dy (rows,256)
-    -> {"dxp": (N,H,W,256), "doffset": (rows,72), "dmask_logits": (rows,36)}."""
+    -> {"dxp": (N,H,W,256), "doffset": (rows,72), "dmask_logits": (rows,36)}.  scatter "atomic": d xp by fp32 atomic adds, equal
+    to rounding between runs; "ordered": the same terms added in ascending source id, equal bits between runs (a workspace is
+    allocated).  doffset and dmask_logits are the same bits in both."""
+    mode = scatter_mode(scatter)
     dev = _dev(xp)
     N, H, W, _ = xp.shape
     rows = _core_rows(N, H, W)
@@ -215,8 +230,14 @@ def dcnv3_core_backward(xp, offset, mask, dy, alloc=None):
     alloc = alloc or _default_alloc(dev)
     out = {"dxp": alloc("dxp", (N, H, W, 256)), "doffset": alloc("doffset", (rows, 72)), "dmask_logits": alloc("dmask_logits", (rows, 36))}
     L = _lib.load()
-    _call(dev, L.gpe_dcnv3_core_backward, "gpe_dcnv3_core_backward", xp.data_ptr(), offset.data_ptr(), mask.data_ptr(), dy.data_ptr(), N, H, W,
-          out["dxp"].data_ptr(), out["doffset"].data_ptr(), out["dmask_logits"].data_ptr(), _stream(dev))
+    if mode == _lib.GPE_SCATTER_ATOMIC:
+        _call(dev, L.gpe_dcnv3_core_backward, "gpe_dcnv3_core_backward", xp.data_ptr(), offset.data_ptr(), mask.data_ptr(), dy.data_ptr(), N, H, W,
+              out["dxp"].data_ptr(), out["doffset"].data_ptr(), out["dmask_logits"].data_ptr(), _stream(dev))
+        return out
+    nbytes = L.gpeo_dcnv3_core_backward_workspace(N, H, W, mode)
+    ws = _ws(alloc, nbytes)
+    _call(dev, L.gpeo_dcnv3_core_backward, "gpeo_dcnv3_core_backward", xp.data_ptr(), offset.data_ptr(), mask.data_ptr(), dy.data_ptr(), N, H, W,
+          out["dxp"].data_ptr(), out["doffset"].data_ptr(), out["dmask_logits"].data_ptr(), _stream(dev), mode, ws.data_ptr(), nbytes)
     return out
 
 
@@ -308,9 +329,12 @@ def enc_forward_save(coor, params, groups=None, alloc=None):
 
 
 @torch.no_grad()
-def enc_backward(params, saved, coor, g_feat, alloc=None):
+def enc_backward(params, saved, coor, g_feat, alloc=None, scatter="atomic"):
     """gpe_map_encoder_backward per coupling batch: from d nocs_feat (B,256,R/8,R/8), coor and what enc_forward_save returned for it
-    (and the same params) -> ({name: gradient} over PARAM_KEYS, the batches' gradients added in batch order, d coor (B,3,R,R))."""
+    (and the same params) -> ({name: gradient} over PARAM_KEYS, the batches' gradients added in batch order, d coor (B,3,R,R)).
+    scatter "atomic": equal to rounding between runs outside ATOMIC_FREE_KEYS; "ordered" (gpeo_map_encoder_backward): equal bits in
+    all of ORDERED_FREE_KEYS and d coor."""
+    mode = scatter_mode(scatter)
     dev = _dev(coor)
     coor = _check_coor(coor, dev)
     B, R = coor.shape[0], coor.shape[2]
@@ -325,11 +349,16 @@ def enc_backward(params, saved, coor, g_feat, alloc=None):
     total, i0 = None, 0
     for N, sv_t in zip(groups, saved):
         grads = {k: alloc(k, s) for k, s in param_shapes().items()}
-        nbytes = L.gpe_map_encoder_backward_workspace(N, R)
+        ordered = mode != _lib.GPE_SCATTER_ATOMIC
+        nbytes = L.gpeo_map_encoder_backward_workspace(N, R, mode) if ordered else L.gpe_map_encoder_backward_workspace(N, R)
         ws = _ws(alloc, nbytes)
         sv, pg = _saved_struct(sv_t, N, R), _params_struct(grads, "grads")
-        _call(dev, L.gpe_map_encoder_backward, "gpe_map_encoder_backward", ctypes.byref(pw), ctypes.byref(sv), coor[i0:i0 + N].data_ptr(),
-              g_feat[i0:i0 + N].data_ptr(), N, R, ctypes.byref(pg), g_coor[i0:i0 + N].data_ptr(), ws.data_ptr(), nbytes, _stream(dev))
+        args = (ctypes.byref(pw), ctypes.byref(sv), coor[i0:i0 + N].data_ptr(), g_feat[i0:i0 + N].data_ptr(), N, R, ctypes.byref(pg),
+                g_coor[i0:i0 + N].data_ptr(), ws.data_ptr(), nbytes, _stream(dev))
+        if ordered:
+            _call(dev, L.gpeo_map_encoder_backward, "gpeo_map_encoder_backward", *args, mode)
+        else:
+            _call(dev, L.gpe_map_encoder_backward, "gpe_map_encoder_backward", *args)
         total = grads if total is None else {k: total[k] + grads[k] for k in PARAM_KEYS}
         i0 += N
     return total, g_coor

@@ -234,6 +234,27 @@ class PoseNet(nn.Module):
     # the same for the two coordinate heads (`xyz_head_backward`, and with it `head_grads_xyz`, `head_grads_feat`, ... and `train_step`)
     _xyz_backward_precision = "fp32"
 
+    # how the map encoder's backward sums d xp of its DCNv3 cores (`map_encoder_backward`, and with it `head_grads_feat`,
+    # `head_grads_backbone`, `train_step` and the accumulated `train_step`)
+    _encoder_scatter = "atomic"
+
+    @property
+    def encoder_scatter(self):
+        """"atomic" (the default) or "ordered": see `set_encoder_scatter`."""
+        return self._encoder_scatter
+
+    def set_encoder_scatter(self, mode):
+        """"atomic" (the default): d xp of the encoder's three DCNv3 cores is scattered with fp32 atomic adds; `map_encoder_backward`
+        and everything that runs through it repeat to rounding between two calls.
+        "ordered": the same terms are added per element in ascending order of their source id, without a floating-point atomic
+        (include/givepose_encgrad_ordered.h): all 48 encoder gradients and d coor, and what is chained below them, are equal bits
+        between two calls.  Slower, and a larger workspace; the forward and the inference path are untouched.
+        Anything else raises ValueError.  Returns self."""
+        from . import enc_grad
+        enc_grad.scatter_mode(mode)
+        self._encoder_scatter = mode
+        return self
+
     @property
     def backward_precision(self):
         """"fp32" (the default) or "bf16": see `set_backward_precision`."""
@@ -1359,7 +1380,9 @@ class PoseNet(nn.Module):
             tensors (features.N.dcnv3.bn.* is never applied and has no entry, as its .grad stays None in the reference),
             "coor": (B,3,R,R), the gradient of the map, "outputs": {"nocs_feat": (B,256,R/8,R/8)} of the fp32 recompute};
         return_saved adds "saved", the list of the batches' saved activations (givepose_amd.enc_grad.saved_shapes).
-        d xp is scattered with fp32 atomics: two calls agree to rounding, not bit for bit (include/givepose_encgrad.h)."""
+        With `encoder_scatter` "atomic" (the default) d xp is scattered with fp32 atomics: two calls agree to rounding, not bit for
+        bit (include/givepose_encgrad.h).  After `set_encoder_scatter("ordered")` d xp is an ordered sum and two calls give equal
+        bits in every entry (include/givepose_encgrad_ordered.h)."""
         from . import enc_grad
         self._enc_backward_supported("map_encoder_backward")
         dev = torch.device(device)
@@ -1368,7 +1391,7 @@ class PoseNet(nn.Module):
         coor = torch.as_tensor(coor).to(dev).to(torch.float32).contiguous()
         groups = self._enc_groups(coor.shape[0], groups)
         saved = enc_grad.enc_forward_save(coor, P, groups=groups)
-        grads, g_coor = enc_grad.enc_backward(P, saved, coor, torch.as_tensor(g_nocs_feat).to(dev))
+        grads, g_coor = enc_grad.enc_backward(P, saved, coor, torch.as_tensor(g_nocs_feat).to(dev), scatter=self._encoder_scatter)
         res = {"param_grads": {"nocs_encoder." + k: v for k, v in grads.items()}, "coor": g_coor,
                "outputs": {"nocs_feat": torch.cat([s["act"][2] for s in saved])}}
         if return_saved:

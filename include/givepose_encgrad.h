@@ -29,7 +29,8 @@
  * the reference do), so everything upstream of a scatter inherits its ordering: this family does NOT claim bit-repeatable results
  * or bitwise linearity.  Without any atomic, and therefore equal between runs bit for bit: in every operator everything but d xp;
  * in the encoder the gradients of the LAST layer's GroupNorm, output_proj, offset, mask, LayerNorm and depth-wise parameters.  Its
- * input_proj and conv gradients, every gradient of the two layers below and d coor follow a scatter.
+ * input_proj and conv gradients, every gradient of the two layers below and d coor follow a scatter.  (givepose_encgrad_ordered.h adds an
+ * opt-in mode in which d xp is an ordered sum and every output is equal bits between runs; the entry points here are its atomic mode.)
  *
  * Memory.  gpe_map_encoder_forward_save writes per crop at R = 64: layer 0 two maps of 64 x 64 x 256 (8 MB), three prefix maps of
  * 1024 x 256 (3 MB), offset and mask (0.4 MB), the pre-norm and the output map (2 MB); a quarter of that for each layer after:
