@@ -46,6 +46,12 @@ Public surface mirrors the reference for this path:
                      tensors in three launches, and the factor of the flat_and_anneal schedule
                      (tools/torch_utils/solver/lr_scheduler.py:177-263), on the device (optim.py, include/givepose_optim.h);
                      train_step runs head_grads_backbone and then the step
+  Adam, AdamW, build_optimizer
+                     the loop's other two FLAGS.optimizer_type choices (engine/train.py:66-72): torch.optim.Adam / AdamW after
+                     clip_grad_norm_, over all tensors in three launches, bit for bit the fp32 restatement of
+                     torch.optim.adam._single_tensor_adam; the interface is Ranger's (step, train_step, GradAccumulator), the
+                     state dict torch's own, so last_optimizer.pth moves both ways (optim.py, include/givepose_adam.h);
+                     build_optimizer(model, optimizer_type, lr) is the loop's choice between the three
   PoseNet.set_repack("host" | "device"), PoseNet.repack_count, repack
                      how the forward's packed weights follow the parameters.  "host" (the default): PoseNet._pack on the host, and
                      params_updated() drops the packed weights and every plan.  "device": the same tensors are written in place on
@@ -74,7 +80,7 @@ Public surface mirrors the reference for this path:
 from .config import PoseNetConfig  # noqa: F401
 from .posenet import PoseNet  # noqa: F401
 from . import bb_grad, enc_grad, optim, pnp_grad, repack, size_grad, xyz_grad  # noqa: F401  (ctypes wrappers only: the library is loaded at the first call)
-from .optim import GradAccumulator, Ranger, clip_grad_norm_, flat_and_anneal_lr  # noqa: F401
+from .optim import Adam, AdamW, GradAccumulator, Ranger, build_optimizer, clip_grad_norm_, flat_and_anneal_lr  # noqa: F401
 
 
 def dcnv3_forward(*args, **kwargs):

@@ -320,6 +320,23 @@ ACCUM_PROTOTYPES = {
 GPC_ACCUM_LAUNCHES, GPC_FLAG_OVERWRITE = 3, 4
 
 
+# Adam / AdamW (include/givepose_adam.h, prefix gpad_; tests/test_adam_cpu.py checks both ways)
+class AdamTensor(Structure):          # gpad_tensor: one parameter of a step (device pointers, host table)
+    _fields_ = [(n, c_void_p) for n in ("p", "g", "m", "v", "vmax")] + [("n", c_longlong), ("step_size", c_float), ("bc2_sqrt", c_float),
+                                                                         ("decay", c_float), ("pad", c_int)]
+
+
+class AdamHyper(Structure):           # gpad_hyper
+    _fields_ = [(n, c_double) for n in ("beta1", "beta2", "eps", "weight_decay", "max_norm")] + [("mode", c_int), ("amsgrad", c_int)]
+
+
+ADAM_PROTOTYPES = {
+    "gpad_adam_step_workspace": ([POINTER(AdamTensor), c_int, POINTER(AdamHyper)], c_longlong),
+    "gpad_adam_step": ([POINTER(AdamTensor), c_int, POINTER(AdamHyper), _P, _P, c_longlong, _P], c_int),
+}
+GPAD_STEP_LAUNCHES, GPAD_MAX_TENSORS, GPAD_MODE_ADAM, GPAD_MODE_ADAMW = 3, 65536, 0, 1
+
+
 
 # the train-mode size head (include/givepose_sizegrad.h, prefix gps_; tests/test_size_train_cpu.py checks both ways)
 class SizeParams(Structure):          # gps_params: size_head's six tensors, weights or their gradients
@@ -404,7 +421,8 @@ def load():
                                       + list(ENCGRAD_ORDERED_PROTOTYPES.items())
                                       + list(BBGRAD_PROTOTYPES.items()) + list(BBGRAD_BF16_PROTOTYPES.items()) + list(OPTIM_PROTOTYPES.items())
                                       + list(SIZEGRAD_PROTOTYPES.items()) + list(ACCUM_PROTOTYPES.items())
-                                      + list(REPACK_PROTOTYPES.items()) + list(TRAINDATA_PROTOTYPES.items())):
+                                      + list(REPACK_PROTOTYPES.items()) + list(TRAINDATA_PROTOTYPES.items())
+                                      + list(ADAM_PROTOTYPES.items())):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.argtypes = argtypes
         fn.restype = restype

@@ -11,6 +11,10 @@ to the host.
 Gradients arrive as `param_grads`, {state_dict name: fp32 device tensor in the parameter's shape}: what PoseNet.head_grads_backbone
 returns.  A parameter registered under two names (ConvModule's .gn / .norm) is one parameter and is updated once.
 
+`Adam` and `AdamW` (include/givepose_adam.h, gpad_*) are the loop's other two FLAGS.optimizer_type choices (engine/train.py:66-72):
+torch.optim.Adam / AdamW with the same interface as `Ranger`, in _lib.GPAD_STEP_LAUNCHES launches, their state dicts in torch's layout;
+`build_optimizer` restates the loop's choice between the three.
+
 `flat_and_anneal_lr` is host arithmetic: the factor on the base rate at iteration `it`.
 
 `GradAccumulator` (include/givepose_accum.h, gpc_*) is the loop's `.grad` when FLAGS.accumulate > 1 or more than one rank trains: one flat
@@ -32,6 +36,10 @@ from .pnp_grad import _default_alloc, _stream
 _TENSOR = np.dtype([("p", "u8"), ("g", "u8"), ("m", "u8"), ("v", "u8"), ("slow", "u8"), ("n", "i8"), ("rows", "i4"), ("row_len", "i4"),
                     ("flags", "i4"), ("step_lr", "f4")])
 _STATE_KEYS = ("exp_avg", "exp_avg_sq", "slow_buffer")
+# gpad_tensor (include/givepose_adam.h), checked against ctypes.sizeof(_lib.AdamTensor) in the same way
+_ADAM_TENSOR = np.dtype([("p", "u8"), ("g", "u8"), ("m", "u8"), ("v", "u8"), ("vmax", "u8"), ("n", "i8"), ("step_size", "f4"), ("bc2_sqrt", "f4"),
+                         ("decay", "f4"), ("pad", "i4")])
+_ADAM_STATE_KEYS = ("exp_avg", "exp_avg_sq", "max_exp_avg_sq")
 
 
 def _describe(t):
@@ -51,6 +59,11 @@ def _check_grad(name, g, dev, shape=None):
 def _table_ptr(tab):
     assert tab.dtype == _TENSOR and tab.flags.c_contiguous and _TENSOR.itemsize == ctypes.sizeof(_lib.OptTensor)
     return tab.ctypes.data_as(ctypes.POINTER(_lib.OptTensor))
+
+
+def _adam_table_ptr(tab):
+    assert tab.dtype == _ADAM_TENSOR and tab.flags.c_contiguous and _ADAM_TENSOR.itemsize == ctypes.sizeof(_lib.AdamTensor)
+    return tab.ctypes.data_as(ctypes.POINTER(_lib.AdamTensor))
 
 
 def _gc_rows(shape, use_gc, gc_conv_only):
@@ -73,7 +86,73 @@ def radam_step_size(step, beta1, beta2, n_sma_threshold):
     return False, 1.0 / (1 - beta1 ** step)
 
 
-class Ranger:
+class _FlatOptimizer:
+    """What the optimisers of this module share: the distinct parameters of a model in model.parameters() order with every name they are
+    registered under, flat fp32 state buffers in which every tensor starts at a multiple of 64 elements, the check of a step's
+    gradients and the workspace."""
+
+    _require_device = True       # the table and the state-dict layout need no device: tests/test_optim_cpu.py builds them on the host
+    _who = "optimizer"
+
+    def _discover(self, model, alloc):
+        """Sets model, params, param_names, _index, device, steps, _offsets and _alloc."""
+        who = self._who
+        self.model = model
+        self.params, self.param_names, self._index = [], [], {}
+        by_ptr = {}
+        for name, p in model.named_parameters(remove_duplicate=False):
+            if (self._require_device and p.device.type != "cuda") or p.dtype != torch.float32 or not p.is_contiguous() or p.numel() < 1:
+                raise ValueError(f"{who}: parameter {name}: {_describe(p)}, expected a non-empty contiguous float32 tensor on a HIP device "
+                                 "(move the model to the device first)")
+            i = by_ptr.get(p.data_ptr())
+            if i is None:
+                i = by_ptr[p.data_ptr()] = len(self.params)
+                self.params.append(p)
+                self.param_names.append(name)
+            elif tuple(self.params[i].shape) != tuple(p.shape):
+                raise ValueError(f"{who}: {name} and {self.param_names[i]} share storage but not a shape")
+            self._index[name] = i
+        if not self.params:
+            raise ValueError(f"{who}: the model has no parameters")
+        if [id(p) for p in model.parameters()] != [id(p) for p in self.params]:
+            raise ValueError(f"{who}: distinct Parameter objects of the model share storage")
+        self.device = self.params[0].device
+        if any(p.device != self.device for p in self.params):
+            raise ValueError(f"{who}: the parameters lie on more than one device")
+        self.steps = [0] * len(self.params)
+        sizes = np.array([p.numel() for p in self.params], np.int64)
+        self._offsets = np.concatenate([[0], np.cumsum((sizes + 63) // 64 * 64)])
+        self._alloc = alloc or _default_alloc(self.device)
+        self._ws = None
+        return sizes
+
+    def _view(self, key, i):
+        o = int(self._offsets[i])
+        return self._flat[key][o:o + self.params[i].numel()].view(self.params[i].shape)
+
+    def _collect(self, param_grads):
+        """{parameter index: gradient} of the names in param_grads, aliases merged."""
+        grads = {}
+        for name, g in param_grads.items():
+            i = self._index.get(name)
+            if i is None:
+                raise ValueError(f"param_grads[{name!r}]: the model has no parameter of that name")
+            _check_grad(name, g, self.device, self.params[i].shape)
+            seen = grads.get(i)
+            if seen is not None and seen[1].data_ptr() != g.data_ptr() and not torch.equal(seen[1], g):
+                raise ValueError(f"param_grads[{name!r}] and param_grads[{seen[0]!r}] name one parameter but carry different gradients")
+            if seen is None:
+                grads[i] = (name, g)
+        return grads
+
+    def _workspace(self, nbytes):
+        if self._ws is None or self._ws.numel() * 4 < nbytes:
+            self._ws = self._alloc("workspace", (max(int(nbytes) // 4, 64),))
+            assert self._ws.data_ptr() % 256 == 0, "workspace buffers must be 256-byte aligned"
+        return self._ws
+
+
+class Ranger(_FlatOptimizer):
     """Ranger over the distinct parameters of `model`, stepped on the device by gpo_ranger_step.
 
     model: a module on a HIP device whose parameters are fp32 and contiguous.  The optimiser owns three flat fp32 device buffers
@@ -82,7 +161,7 @@ class Ranger:
     alloc(name, shape): optional hook that supplies the state buffers, the two device scalars and the workspace (default torch.empty).
     `scalars` holds the gradients' total 2-norm and the clip coefficient of the last step, on the device."""
 
-    _require_device = True       # the table and the state-dict layout need no device: tests/test_optim_cpu.py builds them on the host
+    _who = "Ranger"
 
     def __init__(self, model, lr=1e-3, alpha=0.5, k=6, N_sma_threshhold=5, betas=(0.95, 0.999), eps=1e-5, weight_decay=0, use_gc=True,
                  gc_conv_only=False, gc_loc=True, alloc=None):
@@ -99,40 +178,14 @@ class Ranger:
         if not gc_loc:
             raise NotImplementedError("Ranger: gc_loc=False -- centralising the generalised gradient (after the division by sqrt(v)) is not "
                                       "built; only gc_loc=True, centralising the gradient itself, is")
-        self.model = model
         self.lr, self.alpha, self.k, self.N_sma_threshhold = float(lr), float(alpha), int(k), N_sma_threshhold
         self.betas, self.eps, self.weight_decay = (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
         self.use_gc, self.gc_conv_only, self.gc_loc = bool(use_gc), bool(gc_conv_only), True
-        self.params, self.param_names, self._index = [], [], {}
-        by_ptr = {}
-        for name, p in model.named_parameters(remove_duplicate=False):
-            if (self._require_device and p.device.type != "cuda") or p.dtype != torch.float32 or not p.is_contiguous() or p.numel() < 1:
-                raise ValueError(f"Ranger: parameter {name}: {_describe(p)}, expected a non-empty contiguous float32 tensor on a HIP device "
-                                 "(move the model to the device first)")
-            i = by_ptr.get(p.data_ptr())
-            if i is None:
-                i = by_ptr[p.data_ptr()] = len(self.params)
-                self.params.append(p)
-                self.param_names.append(name)
-            elif tuple(self.params[i].shape) != tuple(p.shape):
-                raise ValueError(f"Ranger: {name} and {self.param_names[i]} share storage but not a shape")
-            self._index[name] = i
-        if not self.params:
-            raise ValueError("Ranger: the model has no parameters")
-        if [id(p) for p in model.parameters()] != [id(p) for p in self.params]:
-            raise ValueError("Ranger: distinct Parameter objects of the model share storage")
-        self.device = self.params[0].device
-        if any(p.device != self.device for p in self.params):
-            raise ValueError("Ranger: the parameters lie on more than one device")
+        sizes = self._discover(model, alloc)
         n = len(self.params)
-        self.steps = [0] * n
-        sizes = np.array([p.numel() for p in self.params], np.int64)
-        self._offsets = np.concatenate([[0], np.cumsum((sizes + 63) // 64 * 64)])
-        self._alloc = alloc or _default_alloc(self.device)
         total = int(self._offsets[-1])
         self._flat = {key: self._alloc(key, (total,)).zero_() for key in _STATE_KEYS}
         self.scalars = self._alloc("scalars", (2,)).zero_()
-        self._ws = None
         st = np.zeros(n, _TENSOR)
         st["p"] = [p.data_ptr() for p in self.params]
         for key, field in zip(_STATE_KEYS, ("m", "v", "slow")):
@@ -144,10 +197,6 @@ class Ranger:
         self._scalar_cache = {}
 
     # ------------------------------------------------------------------ state
-    def _view(self, key, i):
-        o = int(self._offsets[i])
-        return self._flat[key][o:o + self.params[i].numel()].view(self.params[i].shape)
-
     def state_dict(self):
         """torch.optim.Optimizer's layout: state[i] for every parameter that has been stepped, i the index in model.parameters() order;
         param_groups[0]["param_names"] names each index (the first of a shared parameter's names)."""
@@ -182,21 +231,6 @@ class Ranger:
                 self._view(key, int(i)).copy_(s[key])
 
     # ------------------------------------------------------------------ the step
-    def _collect(self, param_grads):
-        """{parameter index: gradient} of the names in param_grads, aliases merged."""
-        grads = {}
-        for name, g in param_grads.items():
-            i = self._index.get(name)
-            if i is None:
-                raise ValueError(f"param_grads[{name!r}]: the model has no parameter of that name")
-            _check_grad(name, g, self.device, self.params[i].shape)
-            seen = grads.get(i)
-            if seen is not None and seen[1].data_ptr() != g.data_ptr() and not torch.equal(seen[1], g):
-                raise ValueError(f"param_grads[{name!r}] and param_grads[{seen[0]!r}] name one parameter but carry different gradients")
-            if seen is None:
-                grads[i] = (name, g)
-        return grads
-
     def _scalars_of(self, step, lr):
         key = (step, lr)
         hit = self._scalar_cache.get(key)
@@ -207,12 +241,6 @@ class Ranger:
                 self._scalar_cache.clear()
             hit = self._scalar_cache[key] = (flags, size * lr)
         return hit
-
-    def _workspace(self, nbytes):
-        if self._ws is None or self._ws.numel() * 4 < nbytes:
-            self._ws = self._alloc("workspace", (max(int(nbytes) // 4, 64),))
-            assert self._ws.data_ptr() % 256 == 0, "workspace buffers must be 256-byte aligned"
-        return self._ws
 
     @torch.no_grad()
     def step(self, param_grads, clip_norm=None, lr=None):
@@ -256,6 +284,173 @@ class Ranger:
             self.model.params_updated()
 
 
+def adam_step_scalars(step, lr, beta1, beta2, weight_decay):
+    """-> (step_size, bias_correction2_sqrt, 1 - lr * weight_decay) of Adam / AdamW at `step`, in Python floats as
+    torch.optim.adam._single_tensor_adam computes them; the device takes each rounded to fp32."""
+    return lr / (1 - beta1 ** step), (1 - beta2 ** step) ** 0.5, 1 - lr * weight_decay
+
+
+class Adam(_FlatOptimizer):
+    """torch.optim.Adam over the distinct parameters of `model`, stepped on the device by gpad_adam_step (include/givepose_adam.h): the
+    `else` branch of the reference's FLAGS.optimizer_type (engine/train.py:66-72).  The arguments and defaults are torch's.
+
+    model: a module on a HIP device whose parameters are fp32 and contiguous.  The optimiser owns the flat fp32 device buffers exp_avg
+    and exp_avg_sq (and max_exp_avg_sq under amsgrad; every tensor starts at a multiple of 64 elements) and updates the parameters in
+    place through their pointers; a step ends with model.params_updated() if the model has one.
+    alloc(name, shape): optional hook that supplies the state buffers, the two device scalars and the workspace (default torch.empty).
+    `scalars` holds the gradients' total 2-norm and the clip coefficient of the last step, on the device.
+    maximize, capturable, differentiable and fused are torch's keywords for paths that are not built: they must be false or None;
+    foreach is accepted and has no meaning here (one launch serves all tensors)."""
+
+    _who = "Adam"
+    _decoupled = False
+    _default_weight_decay = 0
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=None, amsgrad=False, *, foreach=None, maximize=False,
+                 capturable=False, differentiable=False, fused=None, alloc=None):
+        who = self._who
+        weight_decay = self._default_weight_decay if weight_decay is None else weight_decay
+        if torch.is_tensor(lr) or torch.is_tensor(betas[0]) or torch.is_tensor(betas[1]):
+            raise NotImplementedError(f"{who}: a tensor lr or beta is not built; pass Python floats")
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        for key, value in (("maximize", maximize), ("capturable", capturable), ("differentiable", differentiable), ("fused", fused)):
+            if value:
+                raise NotImplementedError(f"{who}: {key}={value!r} is not built; only the plain step is (leave {key} at its default)")
+        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        self.weight_decay, self.amsgrad = float(weight_decay), bool(amsgrad)
+        sizes = self._discover(model, alloc)
+        n, total = len(self.params), int(self._offsets[-1])
+        self._state_keys = _ADAM_STATE_KEYS if self.amsgrad else _ADAM_STATE_KEYS[:2]
+        self._flat = {key: self._alloc(key, (total,)).zero_() for key in self._state_keys}
+        self.scalars = self._alloc("scalars", (2,)).zero_()
+        st = np.zeros(n, _ADAM_TENSOR)
+        st["p"] = [p.data_ptr() for p in self.params]
+        for key, field in zip(self._state_keys, ("m", "v", "vmax")):
+            st[field] = self._flat[key].data_ptr() + 4 * self._offsets[:-1]
+        st["n"] = sizes
+        self._static = st
+        self._scalar_cache = {}
+
+    # ------------------------------------------------------------------ state
+    def _group(self):
+        return {"lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.weight_decay, "amsgrad": self.amsgrad,
+                "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
+                "decoupled_weight_decay": self._decoupled}
+
+    def state_dict(self):
+        """The layout of torch.optim.Adam / AdamW (what the reference's last_optimizer.pth holds, engine/train.py:74-77, 159), so that a
+        dict saved here loads into torch's class and one saved by torch's loads here: state[i] = {"step": 0-d float32 tensor, "exp_avg",
+        "exp_avg_sq"[, "max_exp_avg_sq"]} for every parameter that has been stepped, i the index in model.parameters() order; one
+        param group with torch's keys, and "param_names" naming each index (the first of a shared parameter's names)."""
+        state = {i: {"step": torch.tensor(float(s), dtype=torch.float32), **{key: self._view(key, i).clone() for key in self._state_keys}}
+                 for i, s in enumerate(self.steps) if s > 0}
+        return {"state": state, "param_groups": [{**self._group(), "params": list(range(len(self.params))), "param_names": list(self.param_names)}]}
+
+    def load_state_dict(self, sd):
+        who = f"{self._who}.load_state_dict"
+        groups = sd["param_groups"]
+        if len(groups) != 1 or list(groups[0]["params"]) != list(range(len(self.params))):
+            raise ValueError(f"{who}: one parameter group over {len(self.params)} parameters is expected")
+        g = groups[0]
+        if "param_names" in g and list(g["param_names"]) != self.param_names:
+            bad = [(a, b) for a, b in zip(g["param_names"], self.param_names) if a != b][:3]
+            raise ValueError(f"{who}: the parameter names differ, first {bad}")
+        for key in ("maximize", "capturable", "differentiable", "fused"):
+            if g.get(key):
+                raise NotImplementedError(f"{who}: the saved group has {key}={g[key]!r}, which is not built")
+        if bool(g.get("amsgrad", False)) != self.amsgrad:
+            raise ValueError(f"{who}: the saved group has amsgrad={g.get('amsgrad', False)}, this optimiser was built with amsgrad={self.amsgrad}")
+        if "decoupled_weight_decay" in g and bool(g["decoupled_weight_decay"]) != self._decoupled:
+            raise ValueError(f"{who}: the saved group has decoupled_weight_decay={g['decoupled_weight_decay']} "
+                             f"({'AdamW' if g['decoupled_weight_decay'] else 'Adam'}), this optimiser is {self._who}")
+        for i, s in sd["state"].items():
+            if not 0 <= int(i) < len(self.params):
+                raise ValueError(f"{who}: state index {i} out of range")
+            for key in self._state_keys:
+                if key not in s or tuple(s[key].shape) != tuple(self.params[int(i)].shape):
+                    raise ValueError(f"{who}: state[{i}][{key}] {tuple(s[key].shape) if key in s else 'is missing'}, expected {tuple(self.params[int(i)].shape)}")
+        self.lr, self.betas = float(g["lr"]), (float(g["betas"][0]), float(g["betas"][1]))
+        self.eps, self.weight_decay = float(g["eps"]), float(g["weight_decay"])
+        self._scalar_cache = {}
+        for key in self._state_keys:
+            self._flat[key].zero_()
+        self.steps = [0] * len(self.params)
+        for i, s in sd["state"].items():
+            self.steps[int(i)] = int(float(s["step"]))          # a 0-d tensor (torch >= 1.12) or a number
+            for key in self._state_keys:
+                self._view(key, int(i)).copy_(s[key])
+
+    # ------------------------------------------------------------------ the step
+    def _scalars_of(self, step, lr):
+        key = (step, lr)
+        hit = self._scalar_cache.get(key)
+        if hit is None:
+            if len(self._scalar_cache) > 64:
+                self._scalar_cache.clear()
+            hit = self._scalar_cache[key] = adam_step_scalars(step, lr, self.betas[0], self.betas[1], self.weight_decay)
+        return hit
+
+    @torch.no_grad()
+    def step(self, param_grads, clip_norm=None, lr=None):
+        """One step over the parameters that have an entry in param_grads; a parameter without one is skipped and its step count does
+        not advance (p.grad is None in torch).  clip_norm: clip_grad_norm_'s max_norm over these gradients, applied inside the update
+        (the gradients themselves are not scaled).  lr: this call's learning rate (default: the optimiser's)."""
+        lr = self.lr if lr is None else float(lr)
+        if clip_norm is not None and not float(clip_norm) > 0:
+            raise ValueError(f"{self._who}.step: clip_norm {clip_norm} must be positive (or None)")
+        grads = self._collect(param_grads)
+        if not grads:
+            return
+        active = sorted(grads)
+        L = _lib.load()
+        tab = self._static[active]
+        tab["p"] = [self.params[i].data_ptr() for i in active]
+        tab["g"] = [grads[i][1].data_ptr() for i in active]
+        sc = [self._scalars_of(self.steps[i] + 1, lr) for i in active]
+        tab["step_size"], tab["bc2_sqrt"], tab["decay"] = [s[0] for s in sc], [s[1] for s in sc], [s[2] for s in sc]
+        hyper = _lib.AdamHyper(self.betas[0], self.betas[1], self.eps, self.weight_decay, float(clip_norm) if clip_norm is not None else 0.0,
+                               _lib.GPAD_MODE_ADAMW if self._decoupled else _lib.GPAD_MODE_ADAM, int(self.amsgrad))
+        ptr = _adam_table_ptr(tab)
+        nbytes = L.gpad_adam_step_workspace(ptr, len(active), ctypes.byref(hyper))
+        if nbytes <= 0:
+            _lib.check(-1, "gpad_adam_step_workspace")
+        ws = self._workspace(nbytes)
+        with torch.cuda.device(self.device):
+            _lib.check(L.gpad_adam_step(ptr, len(active), ctypes.byref(hyper), self.scalars.data_ptr(), ws.data_ptr(), ws.numel() * 4,
+                                        _stream(self.device)), "gpad_adam_step")
+        for i in active:
+            self.steps[i] += 1
+        if hasattr(self.model, "params_updated"):
+            self.model.params_updated()
+
+
+class AdamW(Adam):
+    """torch.optim.AdamW (decoupled weight decay, default 1e-2): the 'AdamW' branch of the reference's FLAGS.optimizer_type.  See Adam."""
+
+    _who = "AdamW"
+    _decoupled = True
+    _default_weight_decay = 1e-2
+
+
+def build_optimizer(model, optimizer_type, lr):
+    """The reference's choice of optimiser (engine/train.py:66-72, FLAGS.optimizer_type, FLAGS.lr): 'Ranger' -> Ranger(model, lr=lr),
+    'AdamW' -> AdamW(model, lr=lr), anything else -> Adam(model) at torch's default rate, as the reference builds it."""
+    if optimizer_type == "Ranger":
+        return Ranger(model, lr=lr)
+    if optimizer_type == "AdamW":
+        return AdamW(model, lr=lr)
+    return Adam(model)
+
+
 @torch.no_grad()
 def clip_grad_norm_(param_grads, max_norm, alloc=None):
     """torch.nn.utils.clip_grad_norm_(., max_norm, norm_type=2) over the gradients of param_grads ({name: tensor}; one tensor under two
@@ -293,14 +488,14 @@ class GradAccumulator:
     """The accumulated gradient of the reference's loop (engine/train.py:117-131 with FLAGS.accumulate, and DDP's gradient average) as one
     flat fp32 device buffer in the layout of `optimizer`'s state buffers, filled by gpc_grad_accumulate (include/givepose_accum.h).
 
-    optimizer: a Ranger; the accumulator takes its parameters, names, aliases and offsets.  It owns
+    optimizer: a Ranger, Adam or AdamW; the accumulator takes its parameters, names, aliases and offsets.  It owns
       flat     the accumulated gradients, every tensor at a multiple of 64 elements; the padding is zeroed once and never written;
       stage    a second buffer of the same size for the exchange between ranks, allocated at the first add() with a group;
       scalars  the 2-norm of the accumulated gradients (before the clip) and the clip coefficient of the last add(), on the device.
     alloc(name, shape): optional hook that supplies "flat", "stage", "scalars" and "workspace" (default torch.empty)."""
 
     def __init__(self, optimizer, alloc=None):
-        if not isinstance(optimizer, Ranger):
+        if not isinstance(optimizer, (Ranger, Adam)):        # AdamW is an Adam
             raise ValueError(f"GradAccumulator: a givepose_amd.optim.Ranger is expected, got {type(optimizer).__name__}")
         self.optimizer, self.device = optimizer, optimizer.device
         self._offsets = optimizer._offsets

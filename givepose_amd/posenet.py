@@ -1525,7 +1525,8 @@ class PoseNet(nn.Module):
     def train_step(self, data, pose_loss, optimizer, device="cuda", groups=None, clip_norm=5.0, lr=None, size_head=None):
         """One iteration of the reference's loop (engine/train.py:113-129) for a single batch: `head_grads_backbone` (forward, the six
         loss terms, the backward chain to the image), then optimizer.step(param_grads, clip_norm=clip_norm, lr=lr) with a
-        givepose_amd.optim.Ranger built over this model: clip_grad_norm_ at clip_norm (None: no clipping) fused into one Ranger step on
+        givepose_amd.optim.Ranger, Adam or AdamW built over this model (the only thing checked is `optimizer.model is self`, so any
+        object with Ranger's `step` serves): clip_grad_norm_ at clip_norm (None: no clipping) fused into one optimiser step on
         the device.  The step ends with `params_updated()`, so the next forward repacks the updated weights (on the host: `_pack`).
         -> what `head_grads_backbone` returns (res["loss"] holds the six terms; the gradients in res["param_grads"] are left as computed,
         not scaled by the clip coefficient, which is in optimizer.scalars[1] next to the norm in optimizer.scalars[0]).
