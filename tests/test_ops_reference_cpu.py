@@ -5,6 +5,9 @@
                      correct rounding alone may use all of e_out, half the bound in front of the store and the whole bound behind it
   sensitivity        deliberately wrong float64 implementations (ops_reference.MUTATIONS) are rejected on those same input sets
   closure            every `int gp_*(` of include/givepose_hip.h is mapped to the operator-level test that covers it
+  head kernels       (gp_convnext_stem ... gp_groupnorm_apply_xyz) additionally: every kernel instantiation is taken by some case, the inputs
+                     reach the branches the case comments claim, and the pose decode -- which has no static bound -- rejects its mutants by
+                     the yardstick rule on a well-conditioned float64 reference
 """
 import ast
 import os
@@ -134,15 +137,170 @@ def test_mutation_is_rejected(name, mut):
         assert msg is not None, f"{name} {R.case_id(case)}: mutation {mut} passes the checker (ratio {ratio:.3g})"
 
 
+# ------------------------------------------------------------------------------------------------ head entry and exit kernels
+def _forms(name):
+    if name == "gp_convnext_stem":
+        return {R.stem_form(c) for c in R.STEM_CASES}, R.STEM_FORMS
+    if name == "gp_deconv_col2im":
+        return {R.col2im_form(c) for c in R.COL2IM_CASES}, R.COL2IM_FORMS
+    if name == "gp_xyz_out_layer":
+        return {R.xyz_out_geometry(c)[0] for c in R.XYZ_OUT_CASES}, {"xyz_out<f16>", "xyz_out<f32>"}
+    if name == "gp_pointwise_k3":
+        return {R.pk3_geometry(c)[0] for c in R.PK3_CASES}, {"pointwise_k3<half>", "pointwise_k3<float>"}
+    if name in R.SMALLCIN_CIN:
+        return {R.smallcin_form(name, c) for c in R.SMALLCIN_CASES}, R.SMALLCIN_FORMS[name]
+    if name == "gp_pool_mmm":
+        return {R.pool_geometry(c)[0] for c in R.POOL_CASES}, {"pool_mmm<half>", "pool_mmm<float>"}
+    if name == "gp_size_head":
+        return {R.size_geometry(c)[0] for c in R.SIZE_CASES}, {"size_pool<f16>", "size_pool<f32>"}
+    if name == "gp_attention64":
+        return {R.att_form(c) for c in R.ATT_CASES_32}, {"attention64<half,32>", "attention64<float,32>"}
+    if name == "gp_attention64_hd":
+        return {R.att_form(c) for c in R.ATT_CASES_HD}, {f"attention64<{t},{hd}>" for t in ("half", "float") for hd in (24, 32)}
+    if name == "gp_pose_tail_rt":
+        return {R.pose_form(c) for c in R.POSE_CASES}, {"pose_tail<4>", "pose_tail<6>"}
+    if name == "gp_groupnorm_apply_xyz":
+        return {R.gnxyz_form(c) for c in R.GNXYZ_CASES}, R.GNXYZ_FORMS
+    raise KeyError(name)
+
+
+@pytest.mark.parametrize("name", R.HEAD_OPS)
+def test_every_instantiation_is_taken_by_some_case(name):
+    taken, listed = _forms(name)
+    assert taken == listed, (sorted(listed - taken), sorted(taken - listed))
+    assert sum(1 for n, _, _ in R.MUTATIONS if n == name) >= 2
+
+
+def test_stem_cases():
+    geo = {c: R.stem_geometry(c) for c in R.STEM_CASES}
+    B, H, W = R.STEM_LARGE[:3]
+    form, pxb, rpw = geo[R.STEM_LARGE]
+    factors = (B, H // 4 // rpw, W // 4 // pxb)
+    assert form == "stem_mfma<4>" and factors[0] * factors[1] * factors[2] == 256 and min(factors) > 1      # the threshold itself, every factor of the block index above 1
+    assert [c for c in R.STEM_CASES if c[0] * c[1] * c[2] // 16 * R.STEM_C0 > 600_000] == [R.STEM_LARGE]     # the one LARGE case
+    assert any(c[4] == 0.25 for c in R.STEM_CASES)
+    assert {c[2] // 4 // geo[c][1] for c in R.STEM_CASES} >= {1, 2, 3, 4}                                   # column blocks per row
+    m = R.stem_inputs(R.STEM_CASES[0])["img"].mean((0, 2, 3))
+    assert float(m.abs().min()) > 1.4 and bool((m > 0).any()) and bool((m < 0).any())
+
+
+def test_col2im_summand_counts():
+    for case in R.COL2IM_CASES:
+        B, H, W = case[:3]
+        assert R.col2im_summand_counts(case) == {1: (H + 1) * (W + 1), 2: (H + 1) * (W - 1) + (H - 1) * (W + 1), 4: (H - 1) * (W - 1)}, case
+    assert any(c[1] != c[2] for c in R.COL2IM_CASES)
+
+
+def test_xyz_out_and_pointwise_cases_have_their_tails():
+    geo = [R.xyz_out_geometry(c) for c in R.XYZ_OUT_CASES]
+    assert all(g[4] != 0 for g in geo)                                        # a row tail in every form
+    assert any(g[1] == 1 and g[2] == 64 for g in geo) and any(1 < g[1] < 64 for g in geo)      # several pixels per wave
+    assert any(g[3] == 2 for g in geo) and all(c[0] > 1 and c[1] != c[0] * c[1] for c in R.XYZ_OUT_CASES)
+    for Cout, dt in {(c[1], c[2]) for c in R.PK3_CASES}:
+        geos = [R.pk3_geometry(c) for c in R.PK3_CASES if (c[1], c[2]) == (Cout, dt)]
+        pg = geos[0][1]
+        assert sorted((g[2], g[3]) for g in geos) == [(1, 1), (1, 8 * pg - 1), (2, 1)], (Cout, dt)      # below, one short of and one past a workgroup
+    assert {c[1] for c in R.PK3_CASES if c[2] == torch.float32} == {4, 256, 1024}
+
+
+def test_smallcin_cases_reach_both_edges_and_the_mask_is_soft():
+    B, Rr, Cout, _ = R.SMALLCIN_CASES[0]
+    assert Rr // 2 == 4 and (B * (Rr // 2)) % (256 // (Cout // 4)) != 0         # one pixel quad spans a row; the last block is not full
+    for name in R.SMALLCIN_CIN:
+        for case in R.SMALLCIN_CASES:
+            I = R.smallcin_inputs(name, case)
+            m = I["mask"]
+            assert bool((m == 0).any()) and bool(((m > 0) & (m < 1)).any()) and not bool((m >= 1).any())
+            assert bool((I["xyz4"][:, 3] == 7.0).all())
+    # the masked operand is rounded once to fp32: the float64 reference starts from those values
+    case = R.SMALLCIN_CASES[1]
+    I = R.smallcin_inputs("gp_pnp_conv1_masked", case)
+    x64 = R._smallcin_x(I, "gp_pnp_conv1_masked", case, R.F64)
+    assert torch.equal(x64, x64.float().double()) and bool((x64 == 0).any())
+
+
+def test_pool_and_size_inputs():
+    empty = set()
+    for case in R.POOL_CASES:
+        x = R.pool_inputs(case)["x"]
+        assert bool((x[..., 0] < 0).all()) and bool((x[..., 1] > 0).all()), case
+        empty.add(R.pool_geometry(case)[2] > 0)
+    assert empty == {True, False}                                              # pixel groups that see no pixel, and full ones
+    geo = [R.size_geometry(c) for c in R.SIZE_CASES]
+    assert any(g[1] == 2 and g[2] == 1 for g in geo) and any(g[3] > 0 for g in geo)
+    for case in R.SIZE_CASES:
+        I = R.size_inputs(case)
+        assert bool((I["feat"][..., ::5] < 0).all())
+        n = I["mean_size"].norm(dim=1)
+        assert float(n.max() / n.min()) > 2
+
+
+def test_attention_rows_are_peaked_and_flat():
+    for case in R.ATT_CASES_HD:
+        lead, flat = R.att_row_kinds(R.att_inputs(case), case)
+        assert lead >= R.ATT_PEAK and flat < 0.1, (case, lead, flat)
+
+
+def test_groupnorm_apply_xyz_inputs():
+    for case in R.GNXYZ_CASES:
+        assert R.gnxyz_mean_over_std(R.gnxyz_inputs(case), case) > 18, case
+    assert {c[1] // R.GNXYZ_ROWS for c in R.GNXYZ_CASES} == {1, 25}
+
+
+def test_pose_reference_is_well_conditioned():
+    """Every normalised vector has a norm of at least 0.1 of the logits' scale; every ray is at least 1e-2 rad off the optical axis, but the
+    one crop that lies exactly on it (the angle == 0 branch); per-crop intrinsics differ."""
+    kinds = set()
+    for case in R.POSE_CASES:
+        I = R.pose_inputs(case)
+        o = R.pose_fc(I, case, R.F64)[0]
+        _, (cond, angle) = R.pose_decode(o, I, case)
+        scale = float(o[:, :case[1]].pow(2).mean().sqrt())
+        assert all(float(n.min()) >= 0.1 * scale for n in cond), case
+        assert float(angle[R.POSE_ON_AXIS]) == 0.0, case
+        off = torch.cat([angle[:R.POSE_ON_AXIS], angle[R.POSE_ON_AXIS + 1:]])
+        assert float(off.min()) >= 1e-2, (case, float(off.min()))
+        assert bool((o[:, case[1] + 2] > 0).all())                             # depth in front of the camera
+        fx = I["cam_K"][:, 0]
+        assert len(set(fx.tolist())) == R.POSE_B
+        kinds.add(case[:5])
+    assert len(kinds) == 5 * 2 * 2 * 2 and {c[5] for c in R.POSE_CASES} == {256, 260} and R.POSE_GOLDEN_CALL in R.POSE_CASES
+
+
+@pytest.mark.parametrize("mut", [m for m, _ in R.POSE_DECODE_MUTATIONS])
+def test_pose_decode_mutation_is_rejected(mut):
+    """The decode is held to YARDSTICK x the float32 evaluation's own figure per tensor (floor 2^-24): the float32 evaluation passes it by
+    definition, each mutant must miss it on every case it bears on."""
+    exposing = dict(R.POSE_DECODE_MUTATIONS)[mut]
+    cases = [c for c in R.POSE_CASES if exposing(c)]
+    assert cases
+    for case in cases:
+        I = R.pose_inputs(case)
+        want, ref32 = R.pose_decode_refs(I, case)
+        wrong, _ = R.pose_decode_refs(I, case, mut)
+        fig = R.yardstick_figures(wrong, want, ref32)
+        assert any(dev > R.YARDSTICK * cpu for dev, cpu in fig.values()), (mut, case, fig)
+
+
+def test_pose_decode_float32_figures():
+    worst = {}
+    for case in R.POSE_CASES:
+        want, ref32 = R.pose_decode_refs(R.pose_inputs(case), case)
+        for k, (dev, cpu) in R.yardstick_figures(ref32, want, ref32).items():
+            worst[k] = max(worst.get(k, 0.0), cpu)
+    print("CPU float32 decode figures " + ", ".join(f"{k} {v:.2e}" for k, v in worst.items()))
+    assert all(v < 1e-5 for v in worst.values()), worst
+
+
 # ------------------------------------------------------------------------------------------------ closure
 H = "tests/test_hip_ops.py::"
 S = "tests/test_scalenet_ops_gpu.py::"
 M = "tests/test_misc_ops_conformance.py::"
 E = "tests/test_evalmap_gpu.py::test_kernels_against_reference_fixtures"
-P = "tests/test_pnp_flags_gpu.py::"
 NC = "tests/test_norm_conformance_gpu.py::"
 A = "tests/test_att_pnp_gpu.py::"
 DC = "tests/test_dcnv3_conformance_gpu.py::"
+HC = "tests/test_head_ops_conformance_gpu.py::"
 # entry point -> the operator-level test that holds it against a reference of its own operation (never a whole-network test); graph,
 # timing, version and device-info calls -> the test that exercises them
 CLOSURE = {
@@ -157,7 +315,7 @@ CLOSURE = {
     "gp_convnext_mlp_pack_w2": "tests/test_mlp_conformance_gpu.py::test_pack_w2_bit_exact",
     "gp_convnext_mlp_pack_w2_s32": "tests/test_mlp_conformance_gpu.py::test_pack_w2_bit_exact",
     "gp_convnext_mlp": "tests/test_mlp_conformance_gpu.py::test_mlp_conformance",
-    "gp_convnext_stem": H + "test_stem",
+    "gp_convnext_stem": HC + "test_convnext_stem",
     "gp_dwconv_ln": NC + "test_dwconv_ln",
     "gp_dwconv_ln_groups": M + "test_dwconv_ln_groups",
     "gp_dwconv7_raw_stats": NC + "test_dwconv7_raw_stats",
@@ -166,22 +324,22 @@ CLOSURE = {
     "gp_groupnorm_stats": NC + "test_groupnorm",
     "gp_groupnorm_apply": NC + "test_groupnorm",
     "gp_groupnorm_upsample2x": NC + "test_groupnorm_upsample2x",
-    "gp_groupnorm_apply_xyz": H + "test_groupnorm_apply_xyz",
+    "gp_groupnorm_apply_xyz": HC + "test_groupnorm_apply_xyz",
     "gp_upsample_bilinear2x": NC + "test_upsample_bilinear2x",
-    "gp_deconv_col2im": H + "test_upsample_and_col2im",
-    "gp_xyz_out_layer": H + "test_xyz_out_pointwise_smallcin",
-    "gp_pointwise_k3": H + "test_xyz_out_pointwise_smallcin",
+    "gp_deconv_col2im": HC + "test_deconv_col2im",
+    "gp_xyz_out_layer": HC + "test_xyz_out_layer",
+    "gp_pointwise_k3": HC + "test_pointwise_k3",
     "gp_dcnv3_xyz_project": "tests/test_enc0_xyz.py::test_entry_point_against_float64_reference",
-    "gp_pnp_conv1": H + "test_xyz_out_pointwise_smallcin",
-    "gp_pnp_conv1_masked": P + "test_pnp_conv1_masked_bitwise",
-    "gp_pool_mmm": P + "test_pool_mmm",
-    "gp_xyz_conv3x3_s2": H + "test_xyz_out_pointwise_smallcin",
-    "gp_size_head": H + "test_size_head_golden",
-    "gp_pose_tail": H + "test_pose_tail_golden",
-    "gp_pose_tail_rt": P + "test_pose_tail_rt_golden",
+    "gp_pnp_conv1": HC + "test_smallcin_conv",
+    "gp_pnp_conv1_masked": HC + "test_smallcin_conv",
+    "gp_pool_mmm": HC + "test_pool_mmm",
+    "gp_xyz_conv3x3_s2": HC + "test_smallcin_conv",
+    "gp_size_head": HC + "test_size_head",
+    "gp_pose_tail": HC + "test_pose_tail",
+    "gp_pose_tail_rt": HC + "test_pose_tail_rt",
     "gp_patchify_xyz": M + "test_patchify_xyz",
-    "gp_attention64": A + "test_attention64_hd32_is_attention64",
-    "gp_attention64_hd": A + "test_attention64_hd24",
+    "gp_attention64": HC + "test_attention64",
+    "gp_attention64_hd": HC + "test_attention64_hd",
     "gp_patchify_pnp": A + "test_patchify_pnp_bitwise",
     "gp_resnet_stem": M + "test_resnet_stem",
     "gp_maxpool3x3s2": M + "test_maxpool3x3s2",
