@@ -512,7 +512,8 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 4 ? 2 : 1) void gemm_big_k
             p.C = reinterpret_cast<float*>(pin.C) + (long)blockIdx.y * pin.M * pin.N;
         }
     }
-    static_assert(!PP || (WM * WN == 8 && (NS == 4 || NS == 5) && RB == 64 && !DB), "ping-pong schedule: 8 waves, 4/5-stage ring of 64-byte K steps");
+    static_assert(!PP || (WM * WN == 8 && (NS == 4 || NS == 5) && RB == 64 && !DB) || (WM == 2 && WN == 4 && MT == 8 && NS == 2 && RB == 128 && !DB && !SPL && !R32 && sizeof(T) == 2),
+                  "ping-pong schedule: 8 waves, 4/5-stage ring of 64-byte K steps, or the eight-phase schedule on two buffers of 128-byte K steps");
     constexpr int NW = WM * WN;
     constexpr int BM = WM * MT * 16, BN = WN * NT * 16;
     // RB = bytes of K per LDS row and per K step: 128 (two MFMA k-groups per step) or 64 (one; half the stage
@@ -694,6 +695,144 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 4 ? 2 : 1) void gemm_big_k
     };
 
     constexpr int G = XI + WI;
+    if constexpr (PP && RB == 128) {
+        // ---- Eight-phase schedule on 128-byte K steps (fp16 plain GEMM, scalar-base DMA only; gp_gemm checks eligibility).
+        // A K tile is 64 elements.  LDS holds two buffers (K tile kt lives in buffer kt & 1) of four 16 KB HALF-TILES each: X0, X1, W0, W1,
+        // 128 rows x 128 B in the file's RB == 128 image (16-byte chunk ^= row & 7, applied on the DMA source address).  Half h of X
+        // holds, for each of the two wave rows, the 64 rows of m-tiles 4h .. 4h+3 of that wave; half h of W the 32 rows of n-tiles
+        // 2h, 2h+1 of each of the four wave columns -- so a wave's 128 x 64 tile stays contiguous and the epilogues are untouched.
+        // One half-tile is two LDS-DMA instructions per wave.  A K tile takes four phases, one accumulator quadrant (4 m-tiles x
+        // 2 n-tiles x 2 k-groups = 16 MFMAs) each; a loop iteration is two K tiles = eight phases:
+        //   P1: read W0 (4), read X0 (8) | DMA X1(kt+1) | lgkmcnt(8) | barrier | lgkmcnt(0) | MFMA X0 x W0 | barrier
+        //   P2: read W1 (4)              | DMA W0(kt+2) |            | barrier | lgkmcnt(0) | MFMA X0 x W1 | barrier
+        //   P3: read X1 (8)              | DMA X0(kt+2) |            | barrier | lgkmcnt(0) | MFMA X1 x W0 | barrier
+        //   P4:                          | DMA W1(kt+2) | vmcnt(6)   | barrier |            | MFMA X1 x W1 | barrier
+        // Waves 4-7 start one barrier late (one wave of each group per SIMD, as in the 64-byte schedule below): with the barriers
+        // numbered globally, group 0 runs the front part of phase p in interval 2p and its MFMAs in 2p+1, group 1 in 2p+1 and 2p+2.
+        //   vmcnt: loads retire in issue order.  At P4 of tile kt the three youngest half-tiles (W0, X0, W1 of kt+2: 6 instructions)
+        //        stay in flight; everything older -- X1(kt+1) from P1 and the rest of tile kt+1 from the tile before -- has landed.
+        //        One counted wait per K tile, two per iteration, never 0 before the drain.
+        //   RAW: every wave waits for its own pieces of tile kt+1 in P4 of tile kt (intervals 2p / 2p+1), i.e. before the barrier that
+        //        ends interval 2p+1; the first reads of tile kt+1 are issued in P1 of kt+1 (intervals 2p+2 / 2p+3): one phase later.
+        //   WAR: a half-tile is restaged two phases after the phase that read it last -- X1 read in P3, restaged in the next P1; X0 read
+        //        in P1, restaged in P3; W1 read in P2, restaged in P4: the reads of phase q (group 1: issued in interval 2q+1) are
+        //        retired by the lgkmcnt(0) of that phase (interval 2q+2), before the barrier that opens interval 2q+3, and the
+        //        earliest DMA of phase q+2 (group 0) is issued in interval 2q+4.  W0 alone is restaged ONE phase after its reads (P1 ->
+        //        P2): P1 issues the four W0 reads first (sched_barrier pins the order) and waits lgkmcnt(8) -- LDS reads return in
+        //        order, so the four oldest are back -- before its first barrier; group 1 passes that barrier at the end of interval
+        //        2q+1, group 0's DMA of P2 is issued in interval 2q+2.
+        // K is walked in ascending order for every accumulator (k-group 0, then 1, tile after tile): the 64-byte schedule's bits.
+        // Prologue: hipcc does not count the inline-asm DMAs, so the use of the prefetch registers in prefetch_retire() makes it put a vmcnt(0)
+        // behind the counted vmcnt(6) below -- every workgroup waits for all 14 prologue instructions (112 KB), not only for tile 0 (the 64-byte
+        // schedule has the same wait with half the bytes in flight).  Retiring the prefetch behind the loop would keep 16 more registers
+        // live through it (246 are in use); left as it is.
+        constexpr int HT = 128 * RB;
+        static_assert(STAGE == 4 * HT, "two buffers of four half-tiles");
+        const int grp = wave >> 2;
+        unsigned xo[2][2], wo[2][2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int r = (j * NW + wave) * RPI + lrow;     // row of the half-tile's LDS image
+                const int xr = min((r >> 6) * 128 + h * 64 + (r & 63), p.M - 1 - m0);
+                const int wr = min((r >> 5) * 64 + h * 32 + (r & 31), p.N - 1 - n0);
+                xo[h][j] = (unsigned)(((long)xr * p.ldx + lchunk * EPT) * sizeof(T));
+                wo[h][j] = (unsigned)(((long)wr * p.K + lchunk * EPT) * sizeof(T));
+            }
+        const char* xtile = reinterpret_cast<const char*>(X + (long)m0 * p.ldx);
+        const char* wtile = reinterpret_cast<const char*>(W + (long)n0 * p.K);
+        auto stage_x = [&](int b, int h, int kt) __attribute__((always_inline)) {
+            const char* bx = xtile + (long)kt * RB;
+            const unsigned ls = lds0 + b * STAGE + h * HT + wave * 1024;
+            glds16_s(bx, xo[h][0], ls);
+            glds16_s(bx, xo[h][1], ls + NW * 1024);
+        };
+        auto stage_w = [&](int b, int h, int kt) __attribute__((always_inline)) {
+            const char* bw = wtile + (long)kt * RB;
+            const unsigned ls = lds0 + b * STAGE + (2 + h) * HT + wave * 1024;
+            glds16_s(bw, wo[h][0], ls);
+            glds16_s(bw, wo[h][1], ls + NW * 1024);
+        };
+        const int co0 = (fq ^ sw) << 4, co1 = ((4 + fq) ^ sw) << 4;
+        const char* xfb = smem + (wm * 64 + fr) * RB;
+        const char* wfb = smem + 2 * HT + (wn * 32 + fr) * RB;
+        uint4 xf[2][4][2], wf[2][2][2];      // [half][tile][k-group]
+        auto read_x = [&](int b, int h) __attribute__((always_inline)) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                xf[h][t][0] = *reinterpret_cast<const uint4*>(xfb + b * STAGE + h * HT + t * 16 * RB + co0);
+                xf[h][t][1] = *reinterpret_cast<const uint4*>(xfb + b * STAGE + h * HT + t * 16 * RB + co1);
+            }
+        };
+        auto read_w = [&](int b, int h) __attribute__((always_inline)) {
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                wf[h][t][0] = *reinterpret_cast<const uint4*>(wfb + b * STAGE + h * HT + t * 16 * RB + co0);
+                wf[h][t][1] = *reinterpret_cast<const uint4*>(wfb + b * STAGE + h * HT + t * 16 * RB + co1);
+            }
+        };
+        // second half of a phase: first barrier, the phase's fragments, one accumulator quadrant, second barrier
+        auto quadrant = [&](int xh, int wh) __attribute__((always_inline)) {
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_barrier();
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+                for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                    for (int nt = 0; nt < 2; ++nt) mma<T>(acc[wh * 2 + nt][xh * 4 + mt], wf[wh][nt][ks], xf[xh][mt][ks]);
+            __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        // the four phases of K tile kt in buffer b; s1: tile kt+1 exists beyond its three prefetched half-tiles, s2: tile kt+2 exists
+        auto ktile = [&](int b, int kt, bool s1, bool s2) __attribute__((always_inline)) {
+            read_w(b, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            read_x(b, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            if (s1) stage_x(b ^ 1, 1, kt + 1);
+            asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
+            quadrant(0, 0);
+            read_w(b, 1);
+            __builtin_amdgcn_sched_barrier(0);
+            if (s2) stage_w(b, 0, kt + 2);
+            quadrant(0, 1);
+            read_x(b, 1);
+            __builtin_amdgcn_sched_barrier(0);
+            if (s2) stage_x(b, 0, kt + 2);
+            quadrant(1, 0);
+            if (s2) {
+                stage_w(b, 1, kt + 2);
+                asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+            } else {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+            quadrant(1, 1);
+        };
+        // prologue: tile 0 and the first three half-tiles of tile 1 (gp_gemm: nkt even, >= 4)
+        stage_x(0, 0, 0); stage_w(0, 0, 0); stage_w(0, 1, 0); stage_x(0, 1, 0);
+        stage_w(1, 0, 1); stage_x(1, 0, 1); stage_w(1, 1, 1);
+        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+        prefetch_retire(pfs);
+        __builtin_amdgcn_s_barrier();
+        if (grp) __builtin_amdgcn_s_barrier();
+        clk_stamp(p, 0);
+        for (int kt = 0; kt + 2 < p.nkt; kt += 2) {
+            ktile(0, kt, true, true);
+            ktile(1, kt + 1, true, true);
+        }
+        // drain: the last two tiles; only X1 of the last one is still to be fetched
+        ktile(0, p.nkt - 2, true, false);
+        ktile(1, p.nkt - 1, false, false);
+        clk_stamp(p, 1);
+        if (!grp) __builtin_amdgcn_s_barrier();
+    } else
     if constexpr (PP) {
         // ---- Ping-pong schedule (8 waves = two groups of four, one wave of each group per SIMD).  Per K step a wave
         // runs a LOAD phase [issue its 12 fragment reads of step t | issue the DMA of step t+LEAD | wait for its own
@@ -2201,6 +2340,16 @@ static bool pp_enabled() {
     return on;
 }
 
+static bool pp128_enabled() {   // A/B switch: GP_GEMM_PP128=0 keeps variant 10 on its 64-byte K steps everywhere
+    static const bool on = [] { const char* e = getenv("GP_GEMM_PP128"); return !(e && e[0] == '0'); }();
+    return on;
+}
+
+// shapes on which the eight-phase schedule of variant 10 is the automatic choice (scripts/pp128_ab.py, profiles/pp128_ab.txt): it wins 7-12 % on
+// every product shape with K >= 1024 (stage-2 fc2, stage-3 fc1, the deconv GEMM) and ties at K = 512 (stage-2 fc1 without the weights-in-registers
+// kernel: 0.998 / 1.033), where half of the eight K tiles are prologue and drain -- those stay on the 64-byte schedule
+static bool pp128_wins(int K) { return K >= 1024; }
+
 static bool conv_wide_enabled() {   // A/B switch: GP_CONV_WIDE=0 keeps the 3x3 window conv on 256 x 256 tiles
     static const bool on = [] { const char* e = getenv("GP_CONV_WIDE"); return !(e && e[0] == '0'); }();
     return on;
@@ -2599,6 +2748,27 @@ extern "C" int gp_gemm(const gp_gemm_desc* d, void* stream) {
         GP_LAUNCH_CHECK("gp_gemm");
     }
     if (variant == 10) {   // 256x256 ping-pong: 8 waves of 128x64, 64-byte K steps, 4-stage ring, one workgroup per CU
+        // second schedule of the same tile: eight phases on 128-byte K steps (fp16 plain GEMM through the scalar-base DMA, K a multiple of 128
+        // and >= 256).  Bitwise the 64-byte schedule's results.  Variant 1110 forces it (and fails where it cannot run), 1210 forces the
+        // 64-byte schedule, GP_GEMM_PP128=0 keeps the automatic choice off it (A/B switch).  A timed launch of it reports the entry point
+        // "gp_gemm/pp128" (GP_TIMING_DUMP); the label stays "gemm v10 ...".
+        const int force = p.dbg == 11 ? 1 : p.dbg == 12 ? -1 : 0;
+        if (force) p.dbg = 0;
+        const bool pp128_ok = d->dtype == GP_F16 && !split && !r32 && d->KH == 0 && d->K % 128 == 0 && d->K >= 256 &&
+                              256l * d->ldx * 2 < (1l << 31) && 256l * d->K * 2 < (1l << 31);
+        GP_REQUIRE(force != 1 || pp128_ok, "gp_gemm: variant 1110 (eight-phase schedule) needs a plain fp16 GEMM (no conv, split-operand mode or fp32 residual), "
+                   "K %% 128 == 0, K >= 256 (got K=%d)", d->K);
+        // (the timing ablations and stamps of the 64-byte loop -- variants 110 / 210, GP_PP_STAMPS -- do not exist in the eight-phase loop: any debug code
+        // but the epilogue ones, 3 / 4 / 5, keeps the launch on the 64-byte schedule)
+#ifdef GP_PP_STAMPS
+        const bool dbg_ok = false;
+#else
+        const bool dbg_ok = p.dbg == 0 || (p.dbg >= 3 && p.dbg <= 5);
+#endif
+        if (force == 1 || (force == 0 && dbg_ok && pp128_ok && pp128_enabled() && pp128_wins(d->K))) {
+            launch_big<half_t, 2, 4, 8, 4, 2, false, 128, true>(p, s);
+            GP_LAUNCH_CHECK("gp_gemm/pp128");
+        }
         if (split) launch_big<half_t, 2, 4, 8, 4, 4, false, 64, true, true>(p, s);
         else if (r32) launch_big<half_t, 2, 4, 8, 4, 4, false, 64, true, false, true>(p, s);
         else if (d->dtype == GP_F16) launch_big<half_t, 2, 4, 8, 4, 4, false, 64, true>(p, s); else launch_big<float, 2, 2, 4, 4, 2>(p, s);
