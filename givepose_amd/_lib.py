@@ -32,7 +32,7 @@ class GemmDesc(Structure):
                 ("co_scheduled", c_int), ("prefetch", c_void_p), ("prefetch_bytes", c_long),
                 ("split_shift", c_int), ("x_plane_stride", c_long), ("w_plane_stride", c_long),
                 ("out_planes", c_int), ("c_plane_stride", c_long),
-                ("residual_f32", c_int), ("c16", c_void_p), ("ldc16", c_int), ("gn_rows", c_int)]
+                ("residual_f32", c_int), ("c16", c_void_p), ("ldc16", c_int), ("gn_rows", c_int), ("W_cm", c_void_p)]
 
 
 # name -> argtypes; every symbol include/givepose_hip.h declares (tests/test_abi.py checks both ways)
@@ -398,6 +398,12 @@ TRAINDATA_PROTOTYPES = {
 }
 GPT_MAX_PIXELS, GPT_TRAIN_BATCH_LAUNCHES = 65536, 2
 
+# the weight-pack family (include/givepose_wpack.h, prefix gpw_; tests/test_conv3_pp128_cpu.py checks both ways)
+WPACK_PROTOTYPES = {
+    "gpw_conv3_pack_wcm": ([_P, _P, c_int, c_int, _P], c_int),
+    "gpw_gemm_desc_bytes": ([], c_int),
+}
+
 _lib = None
 
 
@@ -422,12 +428,15 @@ def load():
                                       + list(BBGRAD_PROTOTYPES.items()) + list(BBGRAD_BF16_PROTOTYPES.items()) + list(OPTIM_PROTOTYPES.items())
                                       + list(SIZEGRAD_PROTOTYPES.items()) + list(ACCUM_PROTOTYPES.items())
                                       + list(REPACK_PROTOTYPES.items()) + list(TRAINDATA_PROTOTYPES.items())
-                                      + list(ADAM_PROTOTYPES.items())):
+                                      + list(ADAM_PROTOTYPES.items()) + list(WPACK_PROTOTYPES.items())):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.argtypes = argtypes
         fn.restype = restype
     if lib.gp_version() != ABI_VERSION:      # a stale build would read gp_gemm_desc with another layout
         raise GivePoseHipError(f"{LIB_PATH}: ABI version {lib.gp_version()}, this package needs {ABI_VERSION}: rebuild with "
+                               "`python -m givepose_amd.build`")
+    if lib.gpw_gemm_desc_bytes() != ctypes.sizeof(GemmDesc):      # gp_gemm_desc.W_cm came without a new ABI number: the size tells the layouts apart
+        raise GivePoseHipError(f"{LIB_PATH}: gp_gemm_desc is {lib.gpw_gemm_desc_bytes()} bytes there, {ctypes.sizeof(GemmDesc)} here: rebuild with "
                                "`python -m givepose_amd.build`")
     _lib = lib
     return lib

@@ -51,7 +51,7 @@ def build(force=False, verbose=True):
             os.path.join(HERE, "..", "include", "givepose_bbgrad_bf16.h"), os.path.join(CSRC, "xyz_conv_prec.hpp"),
             os.path.join(HERE, "..", "include", "givepose_xyzgrad_bf16.h"),
             os.path.join(HERE, "..", "include", "givepose_encgrad_ordered.h"), os.path.join(CSRC, "encscatter.hpp"),
-            os.path.join(HERE, "..", "include", "givepose_adam.h")]
+            os.path.join(HERE, "..", "include", "givepose_adam.h"), os.path.join(HERE, "..", "include", "givepose_wpack.h")]
     objs, procs = [], []
     for src in SOURCES:
         s, o = os.path.join(CSRC, src), os.path.join(OBJ, src.replace(".hip", ".o"))

@@ -17,12 +17,14 @@
 // dtype f32: v_mfma_f32_16x16x4_f32 x4 per 16-B chunk (exact fp32 products, fp32 accumulate); the
 //            k order inside a chunk is permuted identically for both operands, which is harmless.
 #include "common.hpp"
+#include "../../include/givepose_wpack.h"
 
 namespace {
 
 struct GemmKP {
     const void* X;
     const void* W;
+    const void* Wcm;   // gp_gemm_desc.W_cm: chunk-major copy of 3x3 weights (conv3_pp128_kernel), or null
     const float* bias;
     const float* gamma;
     const void* res;
@@ -1325,6 +1327,237 @@ __global__ __launch_bounds__(512) void conv3_pp_kernel(const GemmKP p) {
 }
 
 // =====================================================================================================
+// The WIDE window conv (512 pixels x 128 channels, wm = wave & 3, wn = wave >> 2, fp16) on the eight-phase schedule of the ping-pong GEMM
+// (gemm_big_kernel, PP && RB == 128).  W comes from the CHUNK-MAJOR copy Wcm[n][cc][tap][32] (gp_conv3_pack_wcm): the K walk stays channel
+// chunk outer / tap inner, so step s = (chunk s / 9, tap s % 9) is 64 bytes at byte 64 s of a Wcm row, and K TILE j = steps 2j, 2j+1 is one whole
+// 128-byte line per row.  Every ninth K tile straddles two chunks (tap 8 of chunk c, tap 0 of chunk c+1) and reads both window buffers.
+// LDS (128 KB): two W buffers (K tile j in buffer j & 1) of two 8 KB HALF-TILES -- half h holds the 32 rows of n-tiles 2h, 2h+1 of each of the two
+// wave columns, 64 rows x 128 B in the file's RB == 128 image (16-byte chunk ^= row & 7, applied on the DMA source address); one LDS-DMA
+// instruction per wave and half-tile -- then the window double buffer of conv3_pp_kernel, unchanged (chunk g in buffer g & 1, 64-byte pixel
+// slots, the same swizzle, xa / xd addressing).  The X "halves" of a K tile are m-tiles 0-3 / 4-7 read from the window: k-group 0 at the first
+// step's tap shift (and chunk buffer), k-group 1 at the second step's.
+// The loop body is EIGHTEEN K tiles = four chunks (Cin % 128 == 0), fully unrolled, so taps, window buffers, W buffers and DMA counts are
+// immediates; the schedule has a period of nine tiles = two chunks (even chunk in window buffer 0), "tile 0 .. 8" below.  Per K tile:
+//   P1: read W0 (4), read X0 (8) | DMA window slot A | lgkmcnt(8) | barrier | lgkmcnt(0) | MFMA X0 x W0 | barrier
+//   P2: read W1 (4)              | DMA W0(j+2)       |            | barrier | lgkmcnt(0) | MFMA X0 x W1 | barrier
+//   P3: read X1 (8)              | DMA window slot B |            | barrier | lgkmcnt(0) | MFMA X1 x W0 | barrier
+//   P4:                          | DMA W1(j+2)       | vmcnt(N)   | barrier |            | MFMA X1 x W1 | barrier
+// Waves 4-7 start one barrier late: group 0 runs the front part of global phase q in interval 2q and its MFMAs in 2q+1, group 1 in 2q+1 / 2q+2.
+// Window slots: the step with tap t in 1..6 of chunk c carries piece t-1 (wave + 8 (t-1)) of chunk c+1, slot A for the tile's first step, B for
+// its second; the other steps carry nothing (known at compile time).  A piece that does not exist -- index >= NI, or no chunk c+1 -- is still
+// issued, from the zero page: indices NI..47 are the unused tail of the 48 KB buffer, and the buffer of a chunk past the end is never read.
+// W(j+2) past the last tile re-fetches the last tile (into a half-tile whose reads are over; never read).  So the DMA count per phase is fixed.
+//   vmcnt: loads retire in issue order.  N = 2 + (window slots of this tile): W0(j+2), W1(j+2) and the tile's own slots stay in flight,
+//        everything older -- W(j+1) and every window piece issued before this tile -- has landed.  Tile 3 of the body carries the LAST piece
+//        of the odd chunk in slot A (tap 6) and nothing in slot B, and tile 4 reads that chunk: there N = 2, so slot A has landed as well.
+//        (The last piece of the next even chunk is slot B of tile 7; tile 8 has no slots, N = 2 there covers it before tile 0 reads.)
+//        One counted wait per K tile; 0 only in the last tile of the launch (the epilogue reuses the LDS).
+//   RAW: every wave waits for its own pieces of what tile j+1 reads in P4 of tile j, before the barrier that ends that phase's first interval;
+//        the first reads of tile j+1 are issued one phase later (as in the GEMM).
+//   WAR, W: as the GEMM -- W1 read in P2, restaged in P4 (two phases); W0 read in P1, restaged in P2: P1 issues the four W0 reads first and
+//        waits lgkmcnt(8) (LDS reads return in order) before its first barrier, which group 1 passes at the end of interval 2q+1, and group
+//        0's DMA of P2 is issued in interval 2q+2.
+//   WAR, window: buffer 0 (even chunk c) is read last by tile 4 (k-group 0, tap 8), its X1 half in P3 = global phase q: group 1 issues
+//        those reads in interval 2q+1 and retires them (lgkmcnt(0)) in 2q+2, before the barrier that opens 2q+3.  The first piece of chunk
+//        c+2 into buffer 0 is slot A of tile 5 (tap 1 of chunk c+1), phase q+2, issued by group 0 in interval 2q+4 at the earliest.  The
+//        straddling tile itself carries nothing (taps 8 and 0).  Buffer 1 is read last in P3 of tile 8 and restaged from slot B of the next
+//        body's tile 0: three phases later.  So the restaging of buffer (c+1) & 1 never begins before the last read of chunk c-1 retired.
+// K is walked in ascending step order for every accumulator (k-group 0 then 1, tile after tile): conv3_pp_kernel's bits.
+template <int WIMG>
+__global__ __launch_bounds__(512) void conv3_pp128_kernel(const GemmKP p) {
+    constexpr int MT = 8, NT = 4, BM = 512, BN = 128;
+    constexpr int TR = BM / WIMG, WW = (WIMG + 2 + 7) / 8 * 8, NP = (TR + 2) * WW, NI = (NP + 15) / 16;
+    constexpr int WINB = 49152, HT = 8192, WBUF = 2 * HT, WIN0 = 2 * WBUF, XJ = 6;
+    static_assert(WIMG >= 32 && WW % 8 == 0 && WIMG % 8 == 0, "whole rows of one image; the kw deltas must not depend on the m-tile");
+    static_assert(NI <= 48 && NI > 8 * (XJ - 1) && NI * 1024 <= WINB, "six window pieces per wave and chunk, inside the 48 KB buffer");
+    constexpr int SMEM = WIN0 + 2 * WINB;
+    static_assert(SMEM >= 8 * 9216 && SMEM <= 160 * 1024, "LDS");
+    __shared__ __attribute__((aligned(1024))) char smem[SMEM];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave & 3, wn = wave >> 2, grp = wave >> 2;
+    const int fr = lane & 15, fq = lane >> 4, sw = fr & 7;
+
+    const int nblk = p.tiles_m * 2;
+    const int bid = blockIdx.x;
+    const int q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7, idx = bid >> 3;
+    const int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
+    const int m0 = (tile >> 1) * BM, n0 = (tile & 1) * BN;
+    const int img = m0 / (p.H * WIMG), h0 = (m0 - img * p.H * WIMG) / WIMG;
+    const int Cin = p.Cin, NCC = Cin >> 5, NKT = (9 * NCC) >> 1;      // host: Cin % 128 == 0
+
+    const half_t* __restrict__ X = reinterpret_cast<const half_t*>(p.X);
+    const char* zp = reinterpret_cast<const char*>(gp_zero_page_tu);
+
+    // ---- DMA sources.  W: wave w fetches rows 8w .. 8w+7 of a half-tile image, lane l the 16-byte chunk (l & 7) ^ (row & 7) of row l >> 3
+    const unsigned lds0 = (unsigned)(size_t)(lds_char_t*)smem;
+    unsigned woff;
+    {
+        const int r = wave * 8 + (lane >> 3);
+        const int n = n0 + (r >> 5) * 64 + (r & 31);       // (+ 32 h: in the scalar base)
+        woff = (unsigned)(((long)n * p.K + (((lane & 7) ^ (r & 7)) << 3)) * 2);
+    }
+    const char* wcm = reinterpret_cast<const char*>(p.Wcm);
+    const long whalf = 32l * p.K * 2;
+    unsigned xoff[XJ];
+    unsigned xvalid = 0;
+    const char* ximg = reinterpret_cast<const char*>(X + (long)img * p.H * WIMG * Cin);
+    const PfSink pfs = prefetch_issue(p, blockIdx.x, gridDim.x, wave, 8, lane);   // gp_gemm_desc.prefetch (hint)
+    const int lrow = lane >> 2;
+#pragma unroll
+    for (int j = 0; j < XJ; ++j) {
+        const int i = wave + 8 * j, px = i * 16 + lrow;
+        const int wy = px / WW, wx = px - wy * WW;
+        const int gy = h0 - 1 + wy, gx = wx - 1;
+        const int lc = (lane & 3) ^ (((px >> 2) & 1) << 1);
+        const bool ok = i < NI && px < NP && wx < WIMG + 2 && (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)WIMG;
+        xoff[j] = ok ? (unsigned)(((gy * WIMG + gx) * Cin + lc * 8) * 2) : 0u;
+        if (ok) xvalid |= 1u << j;
+    }
+    const unsigned wdst = lds0 + wave * 1024;     // this wave's KB of half 0 of W buffer 0
+    auto stage_w = [&](int bb, int h, int j) __attribute__((always_inline)) {      // half h of K tile min(j, NKT - 1) into W buffer wdst[bb]
+        const char* base = wcm + (long)min(j, NKT - 1) * 128 + h * whalf;
+        glds16_s(base, woff, wdst + bb * WBUF + h * HT);
+    };
+    auto stage_x = [&](int j, int g) __attribute__((always_inline)) {        // piece wave + 8 j of the window of chunk g (zero page where there is none)
+        const unsigned d = lds0 + WIN0 + (g & 1) * WINB + (wave + 8 * j) * 1024;
+        const char* src = ximg + xoff[j] + g * 64;
+        glds16(((xvalid >> j) & 1) && g < NCC ? src : zp, d);
+    };
+
+    f32x4 acc[NT][MT];
+#pragma unroll
+    for (int a = 0; a < NT; ++a) {
+        f32x4 init = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (p.bias) init = *reinterpret_cast<const f32x4*>(p.bias + n0 + wn * 64 + a * 16 + fq * 4);
+#pragma unroll
+        for (int b = 0; b < MT; ++b) acc[a][b] = init;
+    }
+    // window fragment addresses as in conv3_pp_kernel, but ONE register for m-tile 0 of each window buffer: a wave's 128 pixels start at a row
+    // boundary (128 % WIMG == 0), so m-tile mt is pixel (mt * 16 / WIMG) * WW + mt * 16 % WIMG behind m-tile 0 -- a multiple of 8 pixels, which
+    // leaves the swizzle bit alone -- and that distance, the kh shift and nothing else make the immediate offset (<= 17 920)
+    unsigned xa[2];
+    {
+        const int ml = wm * 128 + fr;
+        const int pb = (ml / WIMG) * WW + (ml % WIMG);
+        xa[0] = WIN0 + pb * 64 + ((fq ^ (((pb >> 2) & 1) << 1)) << 4);
+        xa[1] = xa[0] + WINB;
+    }
+    static_assert(128 % WIMG == 0 && WIMG % 16 == 0, "m-tile distances are compile-time constants");
+    unsigned xd[3];
+#pragma unroll
+    for (int kw = 0; kw < 3; ++kw) {
+        const int p0 = fr & 7, p1 = p0 + kw;
+        xd[kw] = kw * 64 + (((fq ^ (((p1 >> 2) & 1) << 1)) - (fq ^ (((p0 >> 2) & 1) << 1))) << 4);
+    }
+    // W fragment (buffer bb, half h, n-tile t, k-group g): wrd[g] + bb * WBUF + h * HT + t * 2048
+    const unsigned wrd[2] = {(unsigned)((wn * 32 + fr) * 128 + ((fq ^ sw) << 4)), (unsigned)((wn * 32 + fr) * 128 + (((4 + fq) ^ sw) << 4))};
+
+    uint4 xf[2][4][2], wf[2][2][2];      // [half][tile][k-group]
+    auto read_w = [&](int bb, int h) __attribute__((always_inline)) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            wf[h][t][0] = *reinterpret_cast<const uint4*>(smem + wrd[0] + bb * WBUF + h * HT + t * 2048);
+            wf[h][t][1] = *reinterpret_cast<const uint4*>(smem + wrd[1] + bb * WBUF + h * HT + t * 2048);
+        }
+    };
+    auto read_x = [&](int h, int s0) __attribute__((always_inline)) {     // s0: first step of the K tile within the body (0 .. 16)
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            const int s = s0 + g, tap = s % 9, kh = tap / 3, kw = tap - kh * 3, wb = s / 9;
+            unsigned xdk = xd[kw];
+            asm volatile("" : "+v"(xdk));   // opaque: keeps hipcc from hoisting xa + xd into 24 loop-invariant registers
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                xf[h][t][g] = *reinterpret_cast<const uint4*>(smem + (xa[wb] + xdk) + kh * WW * 64 + (((h * 4 + t) * 16 / WIMG) * WW + (h * 4 + t) * 16 % WIMG) * 64);
+        }
+    };
+    auto quadrant = [&](int xh, int wh) __attribute__((always_inline)) {
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < 2; ++nt) mma<half_t>(acc[wh * 2 + nt][xh * 4 + mt], wf[wh][nt][ks], xf[xh][mt][ks]);
+        __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    // K tile t18 of the body (global tile j, first chunk of the body c0); last: the launch's last tile
+    auto ktile = [&](int t18, int j, int c0, bool last) __attribute__((always_inline)) {
+        const int bb = t18 & 1, t9 = t18 % 9, s0 = 2 * t9, s1 = s0 + 1;
+        c0 += t18 >= 9 ? 2 : 0;
+        const int tapA = s0 % 9, tapB = s1 % 9;
+        const bool slotA = tapA >= 1 && tapA <= XJ, slotB = tapB >= 1 && tapB <= XJ;
+        read_w(bb, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        read_x(0, s0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (slotA) stage_x(tapA - 1, c0 + s0 / 9 + 1);
+        asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
+        quadrant(0, 0);
+        read_w(bb, 1);
+        __builtin_amdgcn_sched_barrier(0);
+        stage_w(bb, 0, j + 2);
+        quadrant(0, 1);
+        read_x(1, s0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (slotB) stage_x(tapB - 1, c0 + s1 / 9 + 1);
+        quadrant(1, 0);
+        stage_w(bb, 1, j + 2);
+        if (last) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        else wait_vmcnt(t9 == 3 ? 2 : 2 + (slotA ? 1 : 0) + (slotB ? 1 : 0));
+        quadrant(1, 1);
+    };
+
+    // ---- prologue: the window of chunk 0 (all six slots of every wave: a fixed count), W of K tiles 0 and 1
+#pragma unroll
+    for (int j = 0; j < XJ; ++j) stage_x(j, 0);
+    stage_w(0, 0, 0); stage_w(0, 1, 0); stage_w(1, 0, 1); stage_w(1, 1, 1);
+    asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+    prefetch_retire(pfs);
+    __builtin_amdgcn_s_barrier();
+    if (grp) __builtin_amdgcn_s_barrier();
+    clk_stamp(p, 0);
+    const int nbody = NCC >> 2;
+    for (int bd = 0; bd < nbody; ++bd) {
+        const bool lastb = bd + 1 == nbody;
+#pragma unroll
+        for (int t18 = 0; t18 < 18; ++t18) ktile(t18, bd * 18 + t18, bd * 4, t18 == 17 && lastb);
+    }
+    clk_stamp(p, 1);
+    if (!grp) __builtin_amdgcn_s_barrier();
+
+    const int mb = m0 + wm * 128, nb = n0 + wn * 64;
+    char* slab = smem + wave * 9216;
+    switch (p.epi) {
+        case GP_EPI_GELU: epilogue_lean<MT, NT, GP_EPI_GELU>(p, acc, slab, mb, nb, lane); break;
+        case GP_EPI_RELU: epilogue_lean<MT, NT, GP_EPI_RELU>(p, acc, slab, mb, nb, lane); break;
+        default: epilogue_lean<MT, NT, GP_EPI_NONE>(p, acc, slab, mb, nb, lane); break;
+    }
+}
+
+// gpw_conv3_pack_wcm: one thread per 16 bytes of the chunk-major copy, wcm[n][cc][tap][8 q .. 8 q + 7] = w[n][tap][cc * 32 + 8 q ..]
+__global__ __launch_bounds__(256) void conv3_pack_wcm_kernel(const uint4* __restrict__ w, uint4* __restrict__ wcm, long total, int ncc) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int q = (int)(i & 3);
+    long r = i >> 2;
+    const int tap = (int)(r % 9);
+    r /= 9;
+    const int cc = (int)(r % ncc);
+    const long n = r / ncc;
+    wcm[i] = w[((n * 9 + tap) * ncc + cc) * 4 + q];
+}
+
+// =====================================================================================================
 // Weights-in-registers GEMM for K = 512 (variant 16): C[M][N] = act(X[M][512] . W[N][512]^T + bias), fp16.
 // The tile kernels above move every operand byte through an LDS ring, and what a CU can pull from L2 (~53-70 GB/s) is
 // their wall: stage-2 fc1 (M 16384, N 2048, K 512) needs 1.57 MB per CU in 256 x 128 tiles.  With K = 512 a slice of
@@ -2350,6 +2583,14 @@ static bool pp128_enabled() {   // A/B switch: GP_GEMM_PP128=0 keeps variant 10 
 // kernel: 0.998 / 1.033), where half of the eight K tiles are prologue and drain -- those stay on the 64-byte schedule
 static bool pp128_wins(int K) { return K >= 1024; }
 
+static bool conv_pp128_enabled() {   // A/B switch: GP_CONV_PP128=0 keeps the wide window conv on its 64-byte W steps everywhere
+    static const bool on = [] { const char* e = getenv("GP_CONV_PP128"); return !(e && e[0] == '0'); }();
+    return on;
+}
+
+// map widths on which the eight-phase schedule of the wide window conv is the automatic choice (scripts/conv3_pp128_ab.py, profiles/conv3_pp128_ab.txt)
+static bool conv_pp128_wins(int Win) { return Win == 64 || Win == 32; }
+
 static bool conv_wide_enabled() {   // A/B switch: GP_CONV_WIDE=0 keeps the 3x3 window conv on 256 x 256 tiles
     static const bool on = [] { const char* e = getenv("GP_CONV_WIDE"); return !(e && e[0] == '0'); }();
     return on;
@@ -2725,7 +2966,25 @@ extern "C" int gp_gemm(const gp_gemm_desc* d, void* stream) {
         p.tiles_n = 1;
         // wide tile (512 pixels x 128 channels) where it fits: bitwise the 256 x 256 tile's results, 2.3-3.5 % faster (scripts/conv_wide_ab.py,
         // profiles/r04_conv_wide_tile_ab.txt); dbg code 8 (variant 813) forces it, 9 (variant 913) / GP_CONV_WIDE=0 keep the square tile
-        const bool wide = !split && d->Win >= 32 && d->M % 512 == 0 && d->H % (512 / d->Win) == 0 && p.dbg != 9 && (p.dbg == 8 || conv_wide_enabled());
+        // second schedule of the wide tile: eight phases over pairs of (chunk, tap) steps on 128-byte rows of the chunk-major weight copy
+        // (conv3_pp128_kernel; gp_gemm_desc.W_cm from gp_conv3_pack_wcm, Cin a multiple of 128).  Bitwise the 64-byte schedule's results.  Variant
+        // 1113 forces it (and fails where it cannot run), 1213 forces the 64-byte schedule, GP_CONV_PP128=0 keeps the automatic choice off it
+        // (A/B switch).  A timed launch of it reports the entry point "gp_gemm/conv3_pp128" (GP_TIMING_DUMP); the label stays "conv3x3 s1 v13 ...".
+        const int force = p.dbg == 11 ? 1 : p.dbg == 12 ? -1 : 0;
+        if (force) p.dbg = 0;
+        const bool wide_fits = !split && d->Win >= 32 && d->M % 512 == 0 && d->H % (512 / d->Win) == 0;
+        const bool cpp128_ok = wide_fits && d->W_cm != nullptr && ((size_t)d->W_cm & 15) == 0 && d->Cin % 128 == 0 && 256l * d->K * 2 < (1l << 31);
+        GP_REQUIRE(force != 1 || cpp128_ok, "gp_gemm: variant 1113 (eight-phase window conv) needs the wide tile (fp16, no split-operand mode, W in {64, 32}, "
+                   "M %% 512 == 0, whole 512-pixel tiles per image), the chunk-major weight copy W_cm (16-byte aligned) and Cin %% 128 == 0 (got W=%d Cin=%d M=%d W_cm=%s%s)",
+                   d->Win, d->Cin, d->M, d->W_cm ? "set" : "null", split ? ", split" : "");
+        const bool wide = wide_fits && p.dbg != 9 && (p.dbg == 8 || conv_wide_enabled());
+        if (force == 1 || (force == 0 && wide && cpp128_ok && (p.dbg == 0 || p.dbg == 8) && conv_pp128_enabled() && conv_pp128_wins(d->Win))) {
+            p.Wcm = d->W_cm;
+            p.tiles_m = d->M / 512;
+            if (d->Win == 64) hipLaunchKernelGGL((conv3_pp128_kernel<64>), dim3(p.tiles_m * 2), dim3(512), 0, s, p);
+            else hipLaunchKernelGGL((conv3_pp128_kernel<32>), dim3(p.tiles_m * 2), dim3(512), 0, s, p);
+            GP_LAUNCH_CHECK("gp_gemm/conv3_pp128");
+        }
         // 4-stage W ring, DMA lead 2 (a 5-stage / lead-3 instantiation spilled 43 registers and ran 1.6x slower)
         if (split) {
             if (d->Win == 64) hipLaunchKernelGGL((conv3_pp_kernel<64, 4, true>), dim3(p.tiles_m), dim3(512), 0, s, p);
@@ -2824,4 +3083,18 @@ extern "C" int gp_gemm(const gp_gemm_desc* d, void* stream) {
         GP_LAUNCH_CHECK("gp_gemm");
     }
     return gp_fail(GP_ERR_INVALID, "gp_gemm: variant %d not handled", variant);
+}
+
+extern "C" int gpw_gemm_desc_bytes(void) { return (int)sizeof(gp_gemm_desc); }
+
+extern "C" int gpw_conv3_pack_wcm(const void* w, void* wcm, int N, int Cin, void* stream) {
+    GP_REQUIRE(w && wcm && w != wcm, "gpw_conv3_pack_wcm: bad pointers");
+    GP_REQUIRE(N > 0 && Cin > 0 && Cin % 32 == 0, "gpw_conv3_pack_wcm: N=%d, Cin=%d (a multiple of 32)", N, Cin);
+    GP_REQUIRE(((size_t)w & 15) == 0 && ((size_t)wcm & 15) == 0, "gpw_conv3_pack_wcm: 16-byte aligned pointers");
+    const long total = (long)N * 9 * (Cin / 32) * 4;      // 16-byte pieces
+    hipLaunchKernelGGL(conv3_pack_wcm_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const uint4*>(w), reinterpret_cast<uint4*>(wcm), total, Cin / 32);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return gp_fail(GP_ERR_LAUNCH, "gpw_conv3_pack_wcm: %s", hipGetErrorString(e));
+    return GP_OK;
 }

@@ -159,7 +159,7 @@ def auto_splitk(M, N, K, esz, n_cu=256, plain=True):
 
 def gemm(x, w, out, bias=None, epilogue=EPI_NONE, gamma=None, residual=None, M=None, K=None, ldx=None, ldc=None,
          ldres=None, conv=None, splitk=None, variant=0, gn=None, ln=None, prefetch=None, _stamps=None, x_planes=False,
-         out_planes=False, out16=None):
+         out_planes=False, out16=None, w_cm=None):
     """out[m][n] = epi(sum_k x[m][k] w[n][k] + bias[n]).  ``x``/``w`` share dtype (f16|f32); ``out`` is that
     dtype or float32.  conv = dict(B,H,W,Cin,KH,KW,stride,pad) switches X to channels-last implicit GEMM.
     prefetch = a tensor (the weights of the NEXT launch on this stream) to be pulled towards the caches meanwhile: a hint.
@@ -247,6 +247,10 @@ def gemm(x, w, out, bias=None, epilogue=EPI_NONE, gamma=None, residual=None, M=N
         splitk = 1
     d.epilogue, d.out_f32, d.splitk, d.dtype, d.variant = epilogue, out_f32, splitk, code, variant
     d.co_scheduled = 1 if CO_SCHEDULED else 0
+    if w_cm is not None:       # chunk-major copy of 3x3 conv weights (conv3_pack_wcm): gp_gemm_desc.W_cm
+        if conv is None or w_cm.dtype != torch.float16 or tuple(w_cm.shape) != (N, Kw) or not w_cm.is_contiguous() or w_cm.device != x.device:
+            raise TypeError("gemm(w_cm): a contiguous float16 (N, K) tensor on x's device, conv mode only")
+        d.W_cm = w_cm.data_ptr()
     if prefetch is not None:
         d.prefetch, d.prefetch_bytes = prefetch.data_ptr(), prefetch.numel() * prefetch.element_size()
     if ln is not None:       # (row moments (M,2,nslab), column sums of w, nslab, eps): EPI_LNFOLD_GELU
@@ -258,9 +262,29 @@ def gemm(x, w, out, bias=None, epilogue=EPI_NONE, gamma=None, residual=None, M=N
     return out
 
 
+def conv3_pack_wcm(w, out=None):
+    """3x3 conv weights w (Cout, 9 * Cin) fp16 with K = tap * Cin + ci -> the chunk-major copy [n][ci / 32][tap][ci % 32] that
+    conv2d_nhwc(..., w_cm=) hands to the eight-phase window conv (gp_gemm_desc.W_cm).  On the device by gpw_conv3_pack_wcm; a host tensor
+    (PoseNet._pack('cpu')) is permuted where it is -- the same bits, it is a pure permutation."""
+    if w.dtype != torch.float16 or w.dim() != 2:
+        raise TypeError(f"conv3_pack_wcm: a float16 (Cout, 9 * Cin) tensor, got {w.dtype} {tuple(w.shape)}")
+    N, K = w.shape
+    if K % 9 or (K // 9) % 32 or not w.is_contiguous():
+        raise ValueError(f"conv3_pack_wcm: contiguous (Cout, 9 * Cin) weights with Cin % 32 == 0, got {tuple(w.shape)}")
+    cin = K // 9
+    if out is None:
+        out = torch.empty_like(w)
+    if not w.is_cuda:
+        out.copy_(w.view(N, 9, cin // 32, 32).permute(0, 2, 1, 3).reshape(N, K))
+        return out
+    check(_L().gpw_conv3_pack_wcm(_ptr(w), _ptr(out), N, cin, _stream()), "gpw_conv3_pack_wcm")
+    return out
+
+
 def conv2d_nhwc(x, w_packed, KH, KW, stride, pad, out=None, bias=None, epilogue=EPI_NONE, variant=0, gn=None,
-                residual=None, prefetch=None, x_planes=False, out16=None):
-    """Channels-last convolution: x (B,H,W,Cin), w_packed (Cout, KH*KW*Cin) with K = (kh*KW+kw)*Cin+ci."""
+                residual=None, prefetch=None, x_planes=False, out16=None, w_cm=None):
+    """Channels-last convolution: x (B,H,W,Cin), w_packed (Cout, KH*KW*Cin) with K = (kh*KW+kw)*Cin+ci.
+    w_cm: conv3_pack_wcm(w_packed) -- optional, lets a 3x3 s1 p1 Cout-256 launch take the eight-phase window conv."""
     B, H, W_, Cin = x.shape
     Ho = (H + 2 * pad - KH) // stride + 1
     Wo = (W_ + 2 * pad - KW) // stride + 1
@@ -269,7 +293,7 @@ def conv2d_nhwc(x, w_packed, KH, KW, stride, pad, out=None, bias=None, epilogue=
     gemm(x, w_packed, out.view(B * Ho * Wo, -1), bias=bias, epilogue=epilogue,
          residual=None if residual is None else residual.view(B * Ho * Wo, -1),
          conv=dict(B=B, H=H, W=W_, Cin=Cin, KH=KH, KW=KW, stride=stride, pad=pad), variant=variant, gn=gn, prefetch=prefetch,
-         x_planes=x_planes, out16=None if out16 is None else out16.view(B * Ho * Wo, -1))
+         x_planes=x_planes, out16=None if out16 is None else out16.view(B * Ho * Wo, -1), w_cm=w_cm)
     return out
 
 

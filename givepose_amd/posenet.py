@@ -24,6 +24,7 @@ from . import _lib, ops, synth
 from ._lib import (ACT_GELU, ACT_RELU, EPI_GELU, EPI_LNFOLD_GELU, EPI_LRELU, EPI_NONE, EPI_SCALE_RES)
 from .config import FLAT_OPS, ROT_TYPES, PoseNetConfig, validate
 
+CONV3_WCM_LAYERS = (6, 7, 9, 10)      # the xyz heads' 3x3 convs on 32 x 32 and 64 x 64 maps (repack.CONV3_WCM_LAYERS)
 OM_LD = 128     # row length of the DCNv3 offset | mask projection output (108 used columns)
 
 
@@ -375,6 +376,8 @@ class PoseNet(nn.Module):
             W[head + ".gn0_w"], W[head + ".gn0_b"] = f32(h("features.1.weight")), f32(h("features.1.bias"))
             for i in (3, 4, 6, 7, 9, 10):
                 W[f"{head}.c{i}_w"] = gw(h(f"features.{i}.conv.weight").permute(0, 2, 3, 1).reshape(256, -1))
+                if T == torch.float16 and i in CONV3_WCM_LAYERS:     # chunk-major copy for the eight-phase window conv (gp_gemm_desc.W_cm), made once
+                    W[f"{head}.c{i}_wcm"] = ops.conv3_pack_wcm(W[f"{head}.c{i}_w"])
                 W[f"{head}.c{i}_gw"], W[f"{head}.c{i}_gb"] = f32(h(f"features.{i}.norm.weight")), f32(h(f"features.{i}.norm.bias"))
             W[head + ".out_w"], W[head + ".out_b"] = f32(h("out_layer.weight").reshape(3, 256)), f32(h("out_layer.bias"))
         # SizeHead: fold eval BatchNorm1d into conv1 (pose_head.py:34-35)
@@ -624,8 +627,13 @@ class PoseNet(nn.Module):
                     cur = ops.upsample_bilinear2x(cur, buf[f"ya{r}"], out_planes=pl)
             dst = buf[f"yb{r}"] if cur is buf[f"ya{r}"] else buf[f"ya{r}"]
             nxt = {3: 4, 4: 6, 6: 7, 7: 9, 9: 10}.get(i)
+            # (the launches that take the eight-phase window conv read the chunk-major copy: that is what the launch before them prefetches)
+            wide = lambda rr: rr >= 32 and B * rr * rr % 512 == 0 and B * rr * rr > 16384
+            nr = r * 2 if nxt in (6, 9) else r
+            nxt_w = (W.get(f"{head}.c{nxt}_wcm") if wide(nr) else None) if nxt else None
             ops.conv2d_nhwc(cur, W[f"{head}.c{i}_w"], 3, 3, 1, 1, out=dst, gn=self._gnarg(buf, r * r, rows[r]),
-                            prefetch=W[f"{head}.c{nxt}_w"] if nxt else None, x_planes=pl)
+                            prefetch=(nxt_w if nxt_w is not None else W[f"{head}.c{nxt}_w"]) if nxt else None, x_planes=pl,
+                            w_cm=W.get(f"{head}.c{i}_wcm"))
             if i == 10:   # last ConvModule: GN + GELU + the 1x1 out layer in one pass, the 64x64x256 tensor is never written
                 ops.groupnorm_apply_xyz(dst.view(B, r * r, 256), W[f"{head}.c{i}_gw"], W[f"{head}.c{i}_gb"], W[head + ".out_w"],
                                         W[head + ".out_b"], out_nchw, out_nhwc4, 32, ACT_GELU, buf["gn_partial"], rows=rows[r],

@@ -35,6 +35,9 @@ MatFold = namedtuple("MatFold", "A a_off a_rs B b_off b_rs b_f64 add out32 o32_o
 MATRIX_FOLD_KEYS = tuple(f"enc{li}.{k}" for li in range(3) for k in ("fold_w", "fold_b")) + ("enc0.xyz_m",)
 
 
+CONV3_WCM_LAYERS = (6, 7, 9, 10)      # the xyz heads' 3x3 convs on 32 x 32 and 64 x 64 maps: the layers the wide window conv can take
+
+
 class Plan:
     def __init__(self):
         self.entries, self.bnfolds, self.matfolds = [], [], []
@@ -205,6 +208,11 @@ def plan(cfg, compute_dtype=torch.float16, split_gemm=False):
         f32(head + ".gn0_b", h("features.1.bias"))
         for i in (3, 4, 6, 7, 9, 10):
             gw(f"{head}.c{i}_w", h(f"features.{i}.conv.weight").permute(0, 2, 3, 1).reshape(256, -1))
+            if fp16 and i in CONV3_WCM_LAYERS:
+                # ops.conv3_pack_wcm (gpw_conv3_pack_wcm) as a view of the conv weight (256, Cin, 3, 3): [n][ci / 32][tap][ci % 32], the chunk-major
+                # copy the eight-phase window conv reads (gp_gemm_desc.W_cm) -- the dims (n, chunk, tap, ci % 32) with the source strides
+                cin = int(manifest[f"{head}.features.{i}.conv.weight"][1])
+                put(f"{head}.c{i}_wcm", _View(f"{head}.features.{i}.conv.weight", (256, cin // 32, 9, 32), (cin * 9, 32 * 9, 1, 9)).reshape(256, -1), F16)
             f32(f"{head}.c{i}_gw", h(f"features.{i}.norm.weight"))
             f32(f"{head}.c{i}_gb", h(f"features.{i}.norm.bias"))
         f32(head + ".out_w", h("out_layer.weight").reshape(3, 256))

@@ -50,7 +50,7 @@ enum gp_epilogue {
 };
 
 const char* gp_last_error(void);
-#define GP_ABI_VERSION 328 /* 328: + the alignment family gpa_backproject, gpa_umeyama, gpa_crop_depth, declared in givepose_align.h (RANSAC Umeyama pose from the NOCS map and depth); 327: + gp_dcnv3_xyz_project (encoder layer 0 as one gather + one projection); 326: + gp_eval_normalise, gp_eval_pair_overlaps, gp_eval_match, gp_eval_ap (degree-cm / 3D-IoU mAP on the device); 325: + gp_attention64_hd, gp_patchify_pnp, gp_layernorm at non-power-of-two vector counts (C = 192); 324: + gp_pnp_conv1_masked, gp_pool_mmm, gp_pose_tail_rt; round 6: + gp_dwconv_ln_groups (322), gp_convnext_mlp_pack_w2_s32 / GP_MLP_S32 (323); 321 = round 5: gp_gemm_desc.gn_rows + gp_gemm_gn_rows (321); gp_gemm variants 19-22, gp_convnext_mlp C = 512 (no layout change); 311 = round 4 (+ gp_groupnorm_upsample2x); 310 = round 3 (gp_gemm_desc: split-operand / fp32 residual stream fields); 200 = round 2 */
+#define GP_ABI_VERSION 328 /* (gp_gemm_desc.W_cm, appended behind gn_rows, came without a new number: gpw_gemm_desc_bytes of givepose_wpack.h is what the loader checks the layout with) 328: + the alignment family gpa_backproject, gpa_umeyama, gpa_crop_depth, declared in givepose_align.h (RANSAC Umeyama pose from the NOCS map and depth); 327: + gp_dcnv3_xyz_project (encoder layer 0 as one gather + one projection); 326: + gp_eval_normalise, gp_eval_pair_overlaps, gp_eval_match, gp_eval_ap (degree-cm / 3D-IoU mAP on the device); 325: + gp_attention64_hd, gp_patchify_pnp, gp_layernorm at non-power-of-two vector counts (C = 192); 324: + gp_pnp_conv1_masked, gp_pool_mmm, gp_pose_tail_rt; round 6: + gp_dwconv_ln_groups (322), gp_convnext_mlp_pack_w2_s32 / GP_MLP_S32 (323); 321 = round 5: gp_gemm_desc.gn_rows + gp_gemm_gn_rows (321); gp_gemm variants 19-22, gp_convnext_mlp C = 512 (no layout change); 311 = round 4 (+ gp_groupnorm_upsample2x); 310 = round 3 (gp_gemm_desc: split-operand / fp32 residual stream fields); 200 = round 2 */
 int gp_version(void);   /* == GP_ABI_VERSION of the header the library was built from */
 /* device properties the host needs: CU count and arch string ("gfx950...") */
 int gp_device_info(int* cu_count, char* arch, int arch_len);
@@ -187,6 +187,12 @@ typedef struct gp_gemm_desc {
      * consumers take chunks = gn_hw/gn_rows; the small-M kernel (variant 18) only -- gp_gemm fails where it cannot take the launch.  Ask
      * gp_gemm_gn_rows() which value to use for a shape. */
     int gn_rows;
+    /* 3x3 window conv (variant 13) only, optional: the same weights as W in CHUNK-MAJOR order, Wcm[n][ci / 32][kh*3 + kw][ci % 32] (fp16, 16-byte
+     * aligned; gpw_conv3_pack_wcm of givepose_wpack.h makes it from W).  With it, the wide tile and Cin % 128 == 0 the launch runs the eight-phase
+     * schedule on 128-byte weight rows (bitwise the results without it; GP_CONV_PP128=0 keeps the automatic choice off it; variant 1113 forces
+     * it and fails where it cannot run, 1213 forces the 64-byte schedule).  W is still required: every other kernel reads it.  NULL = not available.
+     * The last field: a caller built against the shorter struct is told apart by gpw_gemm_desc_bytes() (givepose_wpack.h), not by GP_ABI_VERSION. */
+    const void* W_cm;
 } gp_gemm_desc;
 /* Rows per statistics chunk the library wants for a fused-GroupNorm fp16 GEMM / conv of M rows (M = B * hw), N columns, K: 64 (the tile kernels'
  * chunk) or, where the small-M latency kernel takes the launch and a smaller tile is faster by its cost model, 32 / 16 (round 5: the heads' 3x3 convs
