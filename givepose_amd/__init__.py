@@ -76,10 +76,16 @@ Public surface mirrors the reference for this path:
                      (tools/dataset_utils.py:32-82), the NOCS / IVFC coordinate targets and their masks, and defor_2D
                      (datasets/data_augmentation.py:11-33) with explicit or seeded draws, in two launches on the device
                      (train_batch.py, include/givepose_traindata.h)
+  ColorAugmenter, color_aug_draws, color_aug
+                     the colour augmentation of a training frame (datasets/load_data_nocs.py:231-237, 559-574, color_aug_type 'new'):
+                     PIL.ImageEnhance's Sharpness, Contrast, Brightness and Color in a drawn order, byte for byte what Pillow gives,
+                     on whole uint8 frames on the device before TrainBatchBuilder crops them, with explicit or seeded plans
+                     (color_aug.py, include/givepose_coloraug.h)
 """
 from .config import PoseNetConfig  # noqa: F401
 from .posenet import PoseNet  # noqa: F401
-from . import bb_grad, enc_grad, optim, pnp_grad, repack, size_grad, xyz_grad  # noqa: F401  (ctypes wrappers only: the library is loaded at the first call)
+from . import bb_grad, color_aug, enc_grad, optim, pnp_grad, repack, size_grad, xyz_grad  # noqa: F401  (ctypes wrappers only: the library is loaded at the first call)
+from .color_aug import ColorAugmenter, color_aug_draws  # noqa: F401
 from .optim import Adam, AdamW, GradAccumulator, Ranger, build_optimizer, clip_grad_norm_, flat_and_anneal_lr  # noqa: F401
 
 

@@ -404,6 +404,15 @@ WPACK_PROTOTYPES = {
     "gpw_gemm_desc_bytes": ([], c_int),
 }
 
+# the colour-augmentation family (include/givepose_coloraug.h, prefix gpca_; tests/test_color_aug_cpu.py checks both ways)
+COLORAUG_PROTOTYPES = {
+    "gpca_luma_partials": ([_P] * 5 + [c_int] * 3 + [_P], c_int),
+    "gpca_apply": ([_P] * 6 + [c_int] * 3 + [_P], c_int),
+}
+GPCA_OP_SKIP, GPCA_OP_NONE, GPCA_OP_SHARPNESS, GPCA_OP_CONTRAST, GPCA_OP_BRIGHTNESS, GPCA_OP_COLOR = -1, 0, 1, 2, 3, 4
+GPCA_BUF_FRAMES, GPCA_BUF_TMP0, GPCA_BUF_TMP1, GPCA_BUF_OUT = 0, 1, 2, 3
+GPCA_PARTIALS, GPCA_STAGE_LAUNCHES, GPCA_MAX_FRAMES = 64, 2, 65535
+
 _lib = None
 
 
@@ -428,7 +437,8 @@ def load():
                                       + list(BBGRAD_PROTOTYPES.items()) + list(BBGRAD_BF16_PROTOTYPES.items()) + list(OPTIM_PROTOTYPES.items())
                                       + list(SIZEGRAD_PROTOTYPES.items()) + list(ACCUM_PROTOTYPES.items())
                                       + list(REPACK_PROTOTYPES.items()) + list(TRAINDATA_PROTOTYPES.items())
-                                      + list(ADAM_PROTOTYPES.items()) + list(WPACK_PROTOTYPES.items())):
+                                      + list(ADAM_PROTOTYPES.items()) + list(WPACK_PROTOTYPES.items())
+                                      + list(COLORAUG_PROTOTYPES.items())):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.argtypes = argtypes
         fn.restype = restype

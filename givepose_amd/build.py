@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "csrc", "build")
 LIB = os.path.join(HERE, "libgivepose_hip.so")
-SOURCES = ["runtime.hip", "gemm.hip", "mlp.hip", "dcnv3.hip", "dcnv3_any.hip", "norm.hip", "misc.hip", "scalenet.hip", "evalmap.hip", "align.hip", "loss.hip", "lossgrad.hip", "pnpgrad.hip", "xyzgrad.hip", "encgrad.hip", "encscatter.hip", "bbgrad.hip", "optim.hip", "sizegrad.hip", "accum.hip", "repack.hip", "traindata.hip", "adam.hip"]
+SOURCES = ["runtime.hip", "gemm.hip", "mlp.hip", "dcnv3.hip", "dcnv3_any.hip", "norm.hip", "misc.hip", "scalenet.hip", "evalmap.hip", "align.hip", "loss.hip", "lossgrad.hip", "pnpgrad.hip", "xyzgrad.hip", "encgrad.hip", "encscatter.hip", "bbgrad.hip", "optim.hip", "sizegrad.hip", "accum.hip", "repack.hip", "traindata.hip", "adam.hip", "coloraug.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wno-unused-value"]
 # The library is built WITHOUT packed-fp32 VALU instructions (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32).  On MI355X a
@@ -51,7 +51,8 @@ def build(force=False, verbose=True):
             os.path.join(HERE, "..", "include", "givepose_bbgrad_bf16.h"), os.path.join(CSRC, "xyz_conv_prec.hpp"),
             os.path.join(HERE, "..", "include", "givepose_xyzgrad_bf16.h"),
             os.path.join(HERE, "..", "include", "givepose_encgrad_ordered.h"), os.path.join(CSRC, "encscatter.hpp"),
-            os.path.join(HERE, "..", "include", "givepose_adam.h"), os.path.join(HERE, "..", "include", "givepose_wpack.h")]
+            os.path.join(HERE, "..", "include", "givepose_adam.h"), os.path.join(HERE, "..", "include", "givepose_wpack.h"),
+            os.path.join(HERE, "..", "include", "givepose_coloraug.h")]
     objs, procs = [], []
     for src in SOURCES:
         s, o = os.path.join(CSRC, src), os.path.join(OBJ, src.replace(".hip", ".o"))

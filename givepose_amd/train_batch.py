@@ -8,8 +8,9 @@ resize_ratio -- and one (3,256) value table per sample: every value of the refer
 function of (sample, channel, byte).  The frames travel as uint8 and two launches, whatever the batch size, write every map.
 
 Not produced: `full_img`, `one_hot`, `roi_img_origin`, `img_scale` and `info_2d` (the training path of this library reads none of
-them), and the colour augmentation (the caller applies it to `frames`).  Instance and frame selection and PNG decoding stay with the
-caller's loader; `fs_net_scale` and `sym_info` let it fill `labels` without the reference on the path.
+them).  The colour augmentation of the frame comes before this builder: color_aug.ColorAugmenter maps `frames` to augmented frames
+on the device, and its output is what is passed here.  Instance and frame selection and PNG decoding stay with the caller's loader;
+`fs_net_scale` and `sym_info` let it fill `labels` without the reference on the path.
 
 The mask deformation draws a uniform random floor(l/2)-subset of the band, the distribution of defor_2D's
 np.random.choice(l, l // 2, replace=False); the STREAM of numpy's legacy generator cannot be reproduced and is not: the subset is the
