@@ -52,7 +52,7 @@ def build(force=False, verbose=True):
             os.path.join(HERE, "..", "include", "givepose_xyzgrad_bf16.h"),
             os.path.join(HERE, "..", "include", "givepose_encgrad_ordered.h"), os.path.join(CSRC, "encscatter.hpp"),
             os.path.join(HERE, "..", "include", "givepose_adam.h"), os.path.join(HERE, "..", "include", "givepose_wpack.h"),
-            os.path.join(HERE, "..", "include", "givepose_coloraug.h")]
+            os.path.join(HERE, "..", "include", "givepose_coloraug.h"), os.path.join(CSRC, "flat_tensors.hpp")]
     objs, procs = [], []
     for src in SOURCES:
         s, o = os.path.join(CSRC, src), os.path.join(OBJ, src.replace(".hip", ".o"))

@@ -1,15 +1,11 @@
 // Adam and AdamW (include/givepose_adam.h, gpad_*): gradient-norm clip + the step over all tensors in three launches.
 //
-//   reduce_kernel    a workgroup per chunk: the chunk's sum of squares of g (clip norm)
-//   finalize_kernel  one workgroup: the chunks' sums of squares added in a fixed order -> norm and clip coefficient (device scalars)
-//   update_kernel    a workgroup per chunk: the element-wise update, every buffer touched once
+//   adam_reduce_kernel  a workgroup per chunk: the chunk's sum of squares of g (clip norm)
+//   finalize_kernel     one workgroup: the chunks' sums of squares added in a fixed order -> norm and clip coefficient (device scalars)
+//   adam_update_kernel  a workgroup per chunk: the element-wise update, every buffer touched once
 //
-// The tables, the chunks and the order of the norm are those of optim.hip for a tensor that is not centralised: a chunk never crosses a
-// tensor; inside it element i belongs to quad i / 4 and the quad to thread (i / 4) % 256, whatever the pointers' alignment.  An aligned
-// quad moves as one 16-byte access, any other as four 4-byte ones: the arithmetic and its order are the same, so the bits do not depend
-// on where a buffer lies.
-#include <vector>
-
+// The tables, the chunks and the order of the norm are those of optim.hip for a tensor that is not centralised: the chunks, the quad rule,
+// the reductions and finalize_kernel are flat_tensors.hpp's, one text for both.
 #include "common.hpp"
 #include "../../include/givepose_adam.h"
 
@@ -19,16 +15,11 @@
 // sequences (__fsqrt_rn is a bare v_sqrt_f32, 1 ulp).
 #pragma clang fp contract(off)
 
+#include "flat_tensors.hpp"
+
 namespace {
 
-constexpr int WG = 256;
-
-struct Chunk {
-    int tensor;
-    int count;               // elements
-    long long start;         // first element
-};
-static_assert(sizeof(gpad_tensor) == 64 && sizeof(Chunk) == 16 && sizeof(gpad_hyper) == 48, "table layout");
+static_assert(sizeof(gpad_tensor) == 64 && sizeof(gpad_hyper) == 48, "table layout");
 
 __device__ __forceinline__ float fmul(float a, float b) {
 #pragma clang fp contract(off)
@@ -48,37 +39,7 @@ __device__ __forceinline__ float fdiv(float a, float b) {
 }
 __device__ __forceinline__ float fsqrt(float a) { return sqrtf(a); }
 
-__device__ __forceinline__ bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-__device__ __forceinline__ float wave_sum(float v) {      // a fixed butterfly: every lane gets the same total
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fadd(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
-// the four waves of a workgroup as (w0 + w1) + (w2 + w3); every thread gets the total
-__device__ __forceinline__ float wg_sum(float v, float* sh, int lane, int wave) {
-    v = wave_sum(v);
-    __syncthreads();
-    if (lane == 0) sh[wave] = v;
-    __syncthreads();
-    return fadd(fadd(sh[0], sh[1]), fadd(sh[2], sh[3]));
-}
-
-__device__ __forceinline__ f32x4 load_quad(const float* p, bool vec) {
-    if (vec) return *(const f32x4*)p;
-    return f32x4{p[0], p[1], p[2], p[3]};
-}
-__device__ __forceinline__ void store_quad(float* p, bool vec, const f32x4& x) {
-    if (vec) {
-        *(f32x4*)p = x;
-    } else {
-        p[0] = x[0], p[1] = x[1], p[2] = x[2], p[3] = x[3];
-    }
-}
-
-// A thread adds the squares of its elements in index order as sq = fma(x, x, sq): what optim.hip's reduce_kernel compiles to (its
-// __fadd_rn(sq, __fmul_rn(x, x)) is contracted to v_fmac_f32), spelled out here so that the norm's bits do not hang on the compiler.
+// the chunk's sum of squares of g, a thread's elements in index order (sq_add)
 __global__ __launch_bounds__(WG) void adam_reduce_kernel(const gpad_tensor* __restrict__ T, const Chunk* __restrict__ C, float* __restrict__ chunk_sq) {
     __shared__ float sh[4];
     const Chunk c = C[blockIdx.x];
@@ -89,27 +50,12 @@ __global__ __launch_bounds__(WG) void adam_reduce_kernel(const gpad_tensor* __re
     for (int q = id; q < nq; q += WG) {
         const f32x4 x = load_quad(g + 4 * q, vec);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) sq = __builtin_fmaf(x[j], x[j], sq);
+        for (int j = 0; j < 4; ++j) sq = sq_add(sq, x[j]);
     }
     if (id == nq % WG)
-        for (int i = 4 * nq; i < c.count; ++i) sq = __builtin_fmaf(g[i], g[i], sq);
+        for (int i = 4 * nq; i < c.count; ++i) sq = sq_add(sq, g[i]);
     const float total = wg_sum(sq, sh, threadIdx.x & 63, threadIdx.x >> 6);
     if (threadIdx.x == 0) chunk_sq[blockIdx.x] = total;
-}
-
-// optim.hip's finalize_kernel, statement for statement: the same sums, the same square root and quotient
-__global__ __launch_bounds__(WG) void adam_finalize_kernel(const float* __restrict__ chunk_sq, int n, float max_norm, float* __restrict__ scal,
-                                                           float* __restrict__ out) {
-    __shared__ float sh[4];
-    float s = 0.0f;
-    for (int i = threadIdx.x; i < n; i += WG) s = __fadd_rn(s, chunk_sq[i]);
-    s = wg_sum(s, sh, threadIdx.x & 63, threadIdx.x >> 6);
-    if (threadIdx.x == 0) {
-        const float norm = __fsqrt_rn(s);
-        const float coef = max_norm > 0.0f ? fminf(1.0f, __fdiv_rn(max_norm, __fadd_rn(norm, 1e-6f))) : 1.0f;
-        scal[0] = norm, scal[1] = coef;
-        if (out) out[0] = norm, out[1] = coef;
-    }
 }
 
 struct Consts {
@@ -183,13 +129,6 @@ __global__ __launch_bounds__(WG) void adam_update_kernel(const gpad_tensor* __re
 }
 
 // ---------------------------------------------------------------------------------- host
-long long up256(long long n) { return (n + 255) / 256 * 256; }
-bool al4(const void* p) { return p && ((uintptr_t)p & 3) == 0; }
-
-struct Plan {
-    long long n_chunks = 0, table_bytes = 0, off_sq = 0, off_scal = 0, total = 0;
-};
-
 int check_hyper(const gpad_hyper* h, const char* name) {
     GP_REQUIRE(h, "%s: null hyper-parameters", name);
     GP_REQUIRE(h->beta1 >= 0 && h->beta1 < 1 && h->beta2 >= 0 && h->beta2 < 1 && h->eps >= 0 && h->weight_decay >= 0,
@@ -207,42 +146,26 @@ int plan_tables(const gpad_tensor* tensors, int n, const gpad_hyper* h, Plan& pl
     for (int i = 0; i < n; ++i) {
         const gpad_tensor& t = tensors[i];
         GP_REQUIRE(t.n >= 1 && t.n < (1LL << 40), "%s: tensor %d has %lld elements", name, i, t.n);
-        GP_REQUIRE(al4(t.g), "%s: tensor %d: g is null or misaligned", name, i);
-        GP_REQUIRE(al4(t.p) && al4(t.m) && al4(t.v) && (h->amsgrad ? al4(t.vmax) : ((uintptr_t)t.vmax & 3) == 0),
+        GP_REQUIRE(t.g && al4(t.g), "%s: tensor %d: g is null or misaligned", name, i);
+        GP_REQUIRE(t.p && t.m && t.v && (t.vmax || !h->amsgrad) && al4(t.p) && al4(t.m) && al4(t.v) && al4(t.vmax),
                    "%s: tensor %d: a null or misaligned pointer", name, i);
         GP_REQUIRE(t.step_size == t.step_size && t.bc2_sqrt > 0.0f && t.decay == t.decay, "%s: tensor %d: step_size %g, bc2_sqrt %g, decay %g", name, i,
                    (double)t.step_size, (double)t.bc2_sqrt, (double)t.decay);
-        chunks += (t.n + GPO_CHUNK - 1) / GPO_CHUNK;
+        chunks += flat_chunks(t.n);
     }
     GP_REQUIRE(chunks < (1LL << 30), "%s: %lld chunks", name, chunks);
-    pl.n_chunks = chunks;
-    pl.table_bytes = (long long)n * sizeof(gpad_tensor) + chunks * (long long)sizeof(Chunk);
-    pl.off_sq = up256(pl.table_bytes);
-    pl.off_scal = pl.off_sq + up256(chunks * 4);
-    pl.total = pl.off_scal + 256;
+    lay_out(pl, n, sizeof(gpad_tensor), chunks);
     if (!stage) return 0;
     stage->resize((size_t)pl.table_bytes);
     gpad_tensor* dt = (gpad_tensor*)stage->data();
-    Chunk* ch = (Chunk*)(stage->data() + (size_t)n * sizeof(gpad_tensor));
-    long long c = 0;
+    Chunk *const ch0 = (Chunk*)(stage->data() + (size_t)n * sizeof(gpad_tensor)), *ch = ch0;
     for (int i = 0; i < n; ++i) {
         dt[i] = tensors[i];
-        for (long long lo = 0; lo < tensors[i].n; lo += GPO_CHUNK) {
-            const long long hi = lo + GPO_CHUNK < tensors[i].n ? lo + GPO_CHUNK : tensors[i].n;
-            ch[c++] = Chunk{i, (int)(hi - lo), lo};
-        }
+        ch = emit_flat(ch, i, 0, tensors[i].n);
     }
-    GP_REQUIRE(c == chunks, "%s: internal chunk count", name);
+    GP_REQUIRE(ch - ch0 == chunks, "%s: internal chunk count", name);
     return 0;
 }
-
-thread_local std::vector<char> g_stage;
-
-#define GPAD_CHECK(name)                                                                              \
-    do {                                                                                              \
-        hipError_t e__ = hipGetLastError();                                                           \
-        if (e__ != hipSuccess) return gp_fail(GP_ERR_LAUNCH, "%s: %s", name, hipGetErrorString(e__)); \
-    } while (0)
 
 }  // namespace
 
@@ -258,22 +181,18 @@ int gpad_adam_step(const gpad_tensor* tensors, int n, const gpad_hyper* h, float
     hipStream_t s = (hipStream_t)stream;
     Plan pl;
     if (int rc = plan_tables(tensors, n, h, pl, &g_stage, name)) return rc;
-    GP_REQUIRE(ws && ((uintptr_t)ws & 255) == 0 && ws_bytes >= pl.total, "%s: workspace of %lld bytes (256-byte aligned) needed, %lld given", name,
-               pl.total, ws_bytes);
-    // pageable source: the runtime has consumed the host buffer when the call returns, so the next step may rewrite it
-    const hipError_t e = hipMemcpyAsync(ws, g_stage.data(), (size_t)pl.table_bytes, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return gp_fail(GP_ERR_RUNTIME, "%s: table copy: %s", name, hipGetErrorString(e));
+    if (int rc = send_tables(pl, ws, ws_bytes, s, name)) return rc;
     char* base = (char*)ws;
     const gpad_tensor* T = (const gpad_tensor*)base;
     const Chunk* C = (const Chunk*)(base + (size_t)n * sizeof(gpad_tensor));
     float *sq = (float*)(base + pl.off_sq), *scal = (float*)(base + pl.off_scal);
     const Consts k{(float)h->beta2, (float)(1.0 - h->beta1), (float)(1.0 - h->beta2), (float)h->eps, (float)h->weight_decay, h->mode, h->amsgrad};
     hipLaunchKernelGGL(adam_reduce_kernel, dim3((unsigned)pl.n_chunks), dim3(WG), 0, s, T, C, sq);
-    GPAD_CHECK(name);
-    hipLaunchKernelGGL(adam_finalize_kernel, dim3(1), dim3(WG), 0, s, (const float*)sq, (int)pl.n_chunks, (float)h->max_norm, scal, scalars);
-    GPAD_CHECK(name);
+    FLAT_CHECK(name);
+    hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(WG), 0, s, (const float*)sq, (int)pl.n_chunks, (float)h->max_norm, scal, scalars);
+    FLAT_CHECK(name);
     hipLaunchKernelGGL(adam_update_kernel, dim3((unsigned)pl.n_chunks), dim3(WG), 0, s, T, C, (const float*)scal, k);
-    GPAD_CHECK(name);
+    FLAT_CHECK(name);
     return 0;
 }
 

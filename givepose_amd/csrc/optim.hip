@@ -5,22 +5,19 @@
 //   update_kernel    a workgroup per chunk: the element-wise Ranger update, every buffer touched once
 //   scale_kernel     gpo_clip_grad_norm only: g *= coef
 //
-// A chunk never crosses a tensor; inside it element i (counted from the row's or the segment's first element) belongs to quad i / 4 and
-// the quad to thread (i / 4) % STRIDE, whatever the pointers' alignment.  An aligned quad moves as one 16-byte access, any other as four
-// 4-byte ones: the arithmetic and its order are the same, so the bits do not depend on where a buffer lies.
-#include <vector>
-
+// The chunks, the quad rule, the reductions and finalize_kernel are flat_tensors.hpp's, shared with accum.hip and adam.hip; here element i
+// of a chunk is counted from the row's or the segment's first element, and a row that fits a chunk is served by a wave (STRIDE 64).
 #include "common.hpp"
 #include "../../include/givepose_optim.h"
 
 // The code of this file asks for no contraction; the __f*_rn wrappers of the runtime's headers are plain operators compiled under the
 // headers' own mode, though, and may still fuse.  Nothing here depends on it: the one exact result, the 0 of a centralised row of
-// length 1, is the single subtraction g - mean.
+// length 1, is the single subtraction g - mean, and the sum of squares is flat_tensors.hpp's sq_add, an fma by its spelling.
 #pragma clang fp contract(off)
 
-namespace {
+#include "flat_tensors.hpp"
 
-constexpr int WG = 256;
+namespace {
 
 struct DevTensor {
     gpo_tensor t;
@@ -28,42 +25,9 @@ struct DevTensor {
     int segs;                // segments per row (1: the row fits a chunk and is served by a wave)
     int pad;
 };
-struct Chunk {
-    int tensor;
-    int count;               // row mode: rows of the run; segment mode: elements
-    long long start;         // row mode: first row; segment mode: first element
-};
-static_assert(sizeof(DevTensor) % 8 == 0 && sizeof(Chunk) == 16, "table layout");
+static_assert(sizeof(DevTensor) == 80, "table layout");
 
 __device__ __forceinline__ bool row_mode(const DevTensor& t) { return t.t.rows > 0 && t.segs == 1; }
-__device__ __forceinline__ bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-__device__ __forceinline__ float wave_sum(float v) {      // a fixed butterfly: every lane gets the same total
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// the four waves of a workgroup as (w0 + w1) + (w2 + w3); every thread gets the total
-__device__ __forceinline__ float wg_sum(float v, float* sh, int lane, int wave) {
-    v = wave_sum(v);
-    __syncthreads();
-    if (lane == 0) sh[wave] = v;
-    __syncthreads();
-    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
-__device__ __forceinline__ f32x4 load_quad(const float* p, bool vec) {
-    if (vec) return *(const f32x4*)p;
-    return f32x4{p[0], p[1], p[2], p[3]};
-}
-__device__ __forceinline__ void store_quad(float* p, bool vec, const f32x4& x) {
-    if (vec) {
-        *(f32x4*)p = x;
-    } else {
-        p[0] = x[0], p[1] = x[1], p[2] = x[2], p[3] = x[3];
-    }
-}
 
 // thread `id` of STRIDE adds its elements of g[0 .. n) to s and their squares to sq, in index order
 template <int STRIDE>
@@ -75,13 +39,13 @@ __device__ __forceinline__ void accumulate(const float* __restrict__ g, int n, i
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             s = __fadd_rn(s, x[j]);
-            sq = __fadd_rn(sq, __fmul_rn(x[j], x[j]));
+            sq = sq_add(sq, x[j]);
         }
     }
     if (id == nq % STRIDE)
         for (int i = 4 * nq; i < n; ++i) {
             s = __fadd_rn(s, g[i]);
-            sq = __fadd_rn(sq, __fmul_rn(g[i], g[i]));
+            sq = sq_add(sq, g[i]);
         }
 }
 
@@ -113,20 +77,6 @@ __global__ __launch_bounds__(WG) void reduce_kernel(const DevTensor* __restrict_
         }
     }
     if (threadIdx.x == 0) chunk_sq[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(WG) void finalize_kernel(const float* __restrict__ chunk_sq, int n, float max_norm, float* __restrict__ scal,
-                                                      float* __restrict__ out) {
-    __shared__ float sh[4];
-    float s = 0.0f;
-    for (int i = threadIdx.x; i < n; i += WG) s = __fadd_rn(s, chunk_sq[i]);
-    s = wg_sum(s, sh, threadIdx.x & 63, threadIdx.x >> 6);
-    if (threadIdx.x == 0) {
-        const float norm = __fsqrt_rn(s);
-        const float coef = max_norm > 0.0f ? fminf(1.0f, __fdiv_rn(max_norm, __fadd_rn(norm, 1e-6f))) : 1.0f;
-        scal[0] = norm, scal[1] = coef;
-        if (out) out[0] = norm, out[1] = coef;
-    }
 }
 
 struct Consts {
@@ -237,13 +187,6 @@ __global__ __launch_bounds__(WG) void scale_kernel(const DevTensor* __restrict__
 }
 
 // ---------------------------------------------------------------------------------- host
-long long up256(long long n) { return (n + 255) / 256 * 256; }
-bool al4(const void* p) { return p && ((uintptr_t)p & 3) == 0; }
-
-struct Plan {
-    long long n_chunks = 0, n_parts = 0, table_bytes = 0, off_sq = 0, off_part = 0, off_scal = 0, total = 0;
-};
-
 // checks the table and lays the workspace out; with `stage` also writes the device tables into it.  clip: only g and n count.
 int plan_tables(const gpo_tensor* tensors, int n, bool clip, Plan& pl, std::vector<char>* stage, const char* name) {
     GP_REQUIRE(tensors && n >= 1 && n <= GPO_MAX_TENSORS, "%s: a table of 1 .. %d tensors is expected (n = %d)", name, GPO_MAX_TENSORS, n);
@@ -251,77 +194,52 @@ int plan_tables(const gpo_tensor* tensors, int n, bool clip, Plan& pl, std::vect
     for (int i = 0; i < n; ++i) {
         const gpo_tensor& t = tensors[i];
         GP_REQUIRE(t.n >= 1 && t.n < (1LL << 40), "%s: tensor %d has %lld elements", name, i, t.n);
-        GP_REQUIRE(al4(t.g), "%s: tensor %d: g is null or misaligned", name, i);
+        GP_REQUIRE(t.g && al4(t.g), "%s: tensor %d: g is null or misaligned", name, i);
         if (clip) {
-            chunks += (t.n + GPO_CHUNK - 1) / GPO_CHUNK;
+            chunks += flat_chunks(t.n);
             continue;
         }
-        GP_REQUIRE(al4(t.p) && al4(t.m) && al4(t.v) && al4(t.slow), "%s: tensor %d: a null or misaligned pointer", name, i);
+        GP_REQUIRE(t.p && t.m && t.v && t.slow && al4(t.p) && al4(t.m) && al4(t.v) && al4(t.slow),
+                   "%s: tensor %d: a null or misaligned pointer", name, i);
         GP_REQUIRE(t.rows >= 0 && (t.rows == 0 || (t.row_len >= 1 && (long long)t.rows * t.row_len == t.n)),
                    "%s: tensor %d: rows %d x row_len %d is not its %lld elements", name, i, t.rows, t.row_len, t.n);
         GP_REQUIRE((t.flags & ~(GPO_FLAG_RECTIFIED | GPO_FLAG_LOOKAHEAD)) == 0, "%s: tensor %d: unknown flags %d", name, i, t.flags);
         if (t.rows == 0) {
-            chunks += (t.n + GPO_CHUNK - 1) / GPO_CHUNK;
+            chunks += flat_chunks(t.n);
         } else if (t.row_len <= GPO_CHUNK) {
             const int per = GPO_CHUNK / t.row_len;
             chunks += (t.rows + per - 1) / per;
             parts += t.rows;
         } else {
-            const long long segs = (t.row_len + GPO_CHUNK - 1) / GPO_CHUNK;
+            const long long segs = flat_chunks(t.row_len);
             chunks += segs * t.rows;
             parts += segs * t.rows;
         }
     }
     GP_REQUIRE(chunks < (1LL << 30), "%s: %lld chunks", name, chunks);
-    pl.n_chunks = chunks, pl.n_parts = parts;
-    pl.table_bytes = (long long)n * sizeof(DevTensor) + chunks * (long long)sizeof(Chunk);
-    pl.off_sq = up256(pl.table_bytes);
-    pl.off_part = pl.off_sq + up256(chunks * 4);
-    pl.off_scal = pl.off_part + up256(parts * 4);
-    pl.total = pl.off_scal + 256;
+    lay_out(pl, n, sizeof(DevTensor), chunks, parts);
     if (!stage) return 0;
     stage->resize((size_t)pl.table_bytes);
     DevTensor* dt = (DevTensor*)stage->data();
-    Chunk* ch = (Chunk*)(stage->data() + (size_t)n * sizeof(DevTensor));
-    long long c = 0, part = 0;
+    Chunk *const ch0 = (Chunk*)(stage->data() + (size_t)n * sizeof(DevTensor)), *ch = ch0;
+    long long part = 0;
     for (int i = 0; i < n; ++i) {
         gpo_tensor t = tensors[i];
         if (clip) t.p = t.m = t.v = t.slow = nullptr, t.rows = t.row_len = t.flags = 0, t.step_lr = 0.0f;
         dt[i] = DevTensor{t, part, 1, 0};
         if (t.rows == 0 || t.row_len > GPO_CHUNK) {
-            const long long L = t.rows ? t.row_len : t.n, nrow = t.rows ? t.rows : 1, segs = (L + GPO_CHUNK - 1) / GPO_CHUNK;
+            const long long L = t.rows ? t.row_len : t.n, nrow = t.rows ? t.rows : 1, segs = flat_chunks(L);
             if (t.rows) dt[i].segs = (int)segs, part += segs * nrow;
-            for (long long r = 0; r < nrow; ++r)
-                for (long long s = 0; s < segs; ++s) {
-                    const long long lo = s * GPO_CHUNK, hi = lo + GPO_CHUNK < L ? lo + GPO_CHUNK : L;
-                    ch[c++] = Chunk{i, (int)(hi - lo), r * L + lo};
-                }
+            for (long long r = 0; r < nrow; ++r) ch = emit_flat(ch, i, r * L, L);
         } else {
             const int per = GPO_CHUNK / t.row_len;
-            for (int r = 0; r < t.rows; r += per) ch[c++] = Chunk{i, t.rows - r < per ? t.rows - r : per, r};
+            for (int r = 0; r < t.rows; r += per) *ch++ = Chunk{i, t.rows - r < per ? t.rows - r : per, r};
             part += t.rows;
         }
     }
-    GP_REQUIRE(c == chunks && part == parts, "%s: internal chunk count", name);
+    GP_REQUIRE(ch - ch0 == chunks && part == parts, "%s: internal chunk count", name);
     return 0;
 }
-
-thread_local std::vector<char> g_stage;
-
-int send_tables(const Plan& pl, void* ws, long long ws_bytes, hipStream_t s, const char* name) {
-    GP_REQUIRE(ws && ((uintptr_t)ws & 255) == 0 && ws_bytes >= pl.total, "%s: workspace of %lld bytes (256-byte aligned) needed, %lld given", name,
-               pl.total, ws_bytes);
-    // pageable source: the runtime has consumed the host buffer when the call returns, so the next step may rewrite it
-    const hipError_t e = hipMemcpyAsync(ws, g_stage.data(), (size_t)pl.table_bytes, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return gp_fail(GP_ERR_RUNTIME, "%s: table copy: %s", name, hipGetErrorString(e));
-    return 0;
-}
-
-#define GPO_CHECK(name)                                                                               \
-    do {                                                                                              \
-        hipError_t e__ = hipGetLastError();                                                           \
-        if (e__ != hipSuccess) return gp_fail(GP_ERR_LAUNCH, "%s: %s", name, hipGetErrorString(e__)); \
-    } while (0)
 
 }  // namespace
 
@@ -348,11 +266,11 @@ int gpo_ranger_step(const gpo_tensor* tensors, int n, const gpo_hyper* h, float*
     const Consts k{(float)h->beta1, (float)h->beta2, (float)(1.0 - h->beta1), (float)(1.0 - h->beta2), (float)h->eps, (float)h->alpha,
                    (float)h->weight_decay};
     hipLaunchKernelGGL(reduce_kernel, dim3((unsigned)pl.n_chunks), dim3(WG), 0, s, T, C, sq, part);
-    GPO_CHECK(name);
+    FLAT_CHECK(name);
     hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(WG), 0, s, (const float*)sq, (int)pl.n_chunks, (float)h->max_norm, scal, scalars);
-    GPO_CHECK(name);
+    FLAT_CHECK(name);
     hipLaunchKernelGGL(update_kernel, dim3((unsigned)pl.n_chunks), dim3(WG), 0, s, T, C, (const float*)part, (const float*)scal, k);
-    GPO_CHECK(name);
+    FLAT_CHECK(name);
     return 0;
 }
 
@@ -373,11 +291,11 @@ int gpo_clip_grad_norm(const gpo_tensor* tensors, int n, float max_norm, float* 
     const Chunk* C = (const Chunk*)(base + (size_t)n * sizeof(DevTensor));
     float *sq = (float*)(base + pl.off_sq), *part = (float*)(base + pl.off_part), *scal = (float*)(base + pl.off_scal);
     hipLaunchKernelGGL(reduce_kernel, dim3((unsigned)pl.n_chunks), dim3(WG), 0, s, T, C, sq, part);
-    GPO_CHECK(name);
+    FLAT_CHECK(name);
     hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(WG), 0, s, (const float*)sq, (int)pl.n_chunks, max_norm, scal, scalars);
-    GPO_CHECK(name);
+    FLAT_CHECK(name);
     hipLaunchKernelGGL(scale_kernel, dim3((unsigned)pl.n_chunks), dim3(WG), 0, s, T, C, (const float*)scal);
-    GPO_CHECK(name);
+    FLAT_CHECK(name);
     return 0;
 }
 

@@ -86,10 +86,36 @@ def radam_step_size(step, beta1, beta2, n_sma_threshold):
     return False, 1.0 / (1 - beta1 ** step)
 
 
+def _workspace(owner, nbytes):
+    """owner._ws grown to nbytes through owner._alloc("workspace", .): the workspace of the optimisers and of the accumulator."""
+    if owner._ws is None or owner._ws.numel() * 4 < nbytes:
+        owner._ws = owner._alloc("workspace", (max(int(nbytes) // 4, 64),))
+        assert owner._ws.data_ptr() % 256 == 0, "workspace buffers must be 256-byte aligned"
+    return owner._ws
+
+
+def _launch(entry, device, workspace, scalars, ptr, n, query_args, args):
+    """One call of the entry point `entry` over the table (ptr, n): `entry`_workspace(ptr, n, *query_args) sizes the workspace, a table it
+    refuses is an error under its name, workspace(nbytes) supplies the buffer and the launch runs under `device`.  scalars: the two
+    device scalars, or a function that allocates them once the workspace exists.  -> scalars"""
+    L = _lib.load()
+    nbytes = getattr(L, entry + "_workspace")(ptr, n, *query_args)
+    if nbytes <= 0:
+        _lib.check(-1, entry + "_workspace")
+    ws = workspace(nbytes)
+    if callable(scalars):
+        scalars = scalars()
+    with torch.cuda.device(device):
+        _lib.check(getattr(L, entry)(ptr, n, *args, scalars.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream(device)), entry)
+    return scalars
+
+
 class _FlatOptimizer:
     """What the optimisers of this module share: the distinct parameters of a model in model.parameters() order with every name they are
-    registered under, flat fp32 state buffers in which every tensor starts at a multiple of 64 elements, the check of a step's
-    gradients and the workspace."""
+    registered under, flat fp32 state buffers in which every tensor starts at a multiple of 64 elements, the loading of a state dict,
+    the check of a step's gradients and the step's skeleton.  A subclass supplies _who, _entry (its entry point, whose size query is
+    `_entry`_workspace), _query_takes_hyper, _ptr (the table's pointer cast), _state_keys, and the methods _take_group, _step_scalars
+    and _fill, with _check_group and _before_step where it has something to check or to prepare."""
 
     _require_device = True       # the table and the state-dict layout need no device: tests/test_optim_cpu.py builds them on the host
     _who = "optimizer"
@@ -145,11 +171,87 @@ class _FlatOptimizer:
                 grads[i] = (name, g)
         return grads
 
-    def _workspace(self, nbytes):
-        if self._ws is None or self._ws.numel() * 4 < nbytes:
-            self._ws = self._alloc("workspace", (max(int(nbytes) // 4, 64),))
-            assert self._ws.data_ptr() % 256 == 0, "workspace buffers must be 256-byte aligned"
-        return self._ws
+    def _make_state(self, sizes, dtype, fields):
+        """The flat state buffers (_state_keys, the table's `fields`), the scalars and the table columns that no step changes."""
+        total = int(self._offsets[-1])
+        self._flat = {key: self._alloc(key, (total,)).zero_() for key in self._state_keys}
+        self.scalars = self._alloc("scalars", (2,)).zero_()
+        st = np.zeros(len(self.params), dtype)
+        st["p"] = [p.data_ptr() for p in self.params]
+        for key, field in zip(self._state_keys, fields):
+            st[field] = self._flat[key].data_ptr() + 4 * self._offsets[:-1]
+        st["n"] = sizes
+        self._static = st
+        self._scalar_cache = {}
+
+    # ------------------------------------------------------------------ state
+    def _check_group(self, g, who):
+        pass
+
+    def load_state_dict(self, sd):
+        who = f"{self._who}.load_state_dict"
+        groups = sd["param_groups"]
+        if len(groups) != 1 or list(groups[0]["params"]) != list(range(len(self.params))):
+            raise ValueError(f"{who}: one parameter group over {len(self.params)} parameters is expected")
+        g = groups[0]
+        if "param_names" in g and list(g["param_names"]) != self.param_names:
+            bad = [(a, b) for a, b in zip(g["param_names"], self.param_names) if a != b][:3]
+            raise ValueError(f"{who}: the parameter names differ, first {bad}")
+        self._check_group(g, who)
+        for i, s in sd["state"].items():
+            if not 0 <= int(i) < len(self.params):
+                raise ValueError(f"{who}: state index {i} out of range")
+            for key in self._state_keys:
+                if key not in s or tuple(s[key].shape) != tuple(self.params[int(i)].shape):
+                    raise ValueError(f"{who}: state[{i}][{key}] {tuple(s[key].shape) if key in s else 'is missing'}, expected {tuple(self.params[int(i)].shape)}")
+        self._take_group(g)
+        self._scalar_cache = {}
+        for key in self._state_keys:
+            self._flat[key].zero_()
+        self.steps = [0] * len(self.params)
+        for i, s in sd["state"].items():
+            self.steps[int(i)] = int(float(s["step"]))          # a number, or torch's 0-d tensor (torch >= 1.12)
+            for key in self._state_keys:
+                self._view(key, int(i)).copy_(s[key])
+
+    # ------------------------------------------------------------------ the step
+    def _scalars_of(self, step, lr):
+        key = (step, lr)
+        hit = self._scalar_cache.get(key)
+        if hit is None:
+            if len(self._scalar_cache) > 64:
+                self._scalar_cache.clear()
+            hit = self._scalar_cache[key] = self._step_scalars(step, lr)
+        return hit
+
+    def _before_step(self, active):
+        pass
+
+    @torch.no_grad()
+    def step(self, param_grads, clip_norm=None, lr=None):
+        """One step over the parameters that have an entry in param_grads; a parameter without one is skipped and its step count does
+        not advance (p.grad is None in the reference and in torch).  clip_norm: clip_grad_norm_'s max_norm over these gradients, applied
+        inside the update (the gradients themselves are not scaled).  lr: this call's learning rate (default: the optimiser's).  The
+        step counts advance after the launch, so a refused step leaves them alone."""
+        lr = self.lr if lr is None else float(lr)
+        if clip_norm is not None and not float(clip_norm) > 0:
+            raise ValueError(f"{self._who}.step: clip_norm {clip_norm} must be positive (or None)")
+        grads = self._collect(param_grads)
+        if not grads:
+            return
+        active = sorted(grads)
+        self._before_step(active)
+        tab = self._static[active]
+        tab["p"] = [self.params[i].data_ptr() for i in active]
+        tab["g"] = [grads[i][1].data_ptr() for i in active]
+        hyper = self._fill(tab, [self._scalars_of(self.steps[i] + 1, lr) for i in active], float(clip_norm) if clip_norm is not None else 0.0)
+        h = ctypes.byref(hyper)
+        _launch(self._entry, self.device, lambda nbytes: _workspace(self, nbytes), self.scalars, self._ptr(tab), len(active),
+                (h,) if self._query_takes_hyper else (), (h,))
+        for i in active:
+            self.steps[i] += 1
+        if hasattr(self.model, "params_updated"):
+            self.model.params_updated()
 
 
 class Ranger(_FlatOptimizer):
@@ -161,7 +263,9 @@ class Ranger(_FlatOptimizer):
     alloc(name, shape): optional hook that supplies the state buffers, the two device scalars and the workspace (default torch.empty).
     `scalars` holds the gradients' total 2-norm and the clip coefficient of the last step, on the device."""
 
-    _who = "Ranger"
+    _who, _entry, _query_takes_hyper = "Ranger", "gpo_ranger_step", False
+    _ptr = staticmethod(_table_ptr)
+    _state_keys = _STATE_KEYS
 
     def __init__(self, model, lr=1e-3, alpha=0.5, k=6, N_sma_threshhold=5, betas=(0.95, 0.999), eps=1e-5, weight_decay=0, use_gc=True,
                  gc_conv_only=False, gc_loc=True, alloc=None):
@@ -181,20 +285,9 @@ class Ranger(_FlatOptimizer):
         self.lr, self.alpha, self.k, self.N_sma_threshhold = float(lr), float(alpha), int(k), N_sma_threshhold
         self.betas, self.eps, self.weight_decay = (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
         self.use_gc, self.gc_conv_only, self.gc_loc = bool(use_gc), bool(gc_conv_only), True
-        sizes = self._discover(model, alloc)
-        n = len(self.params)
-        total = int(self._offsets[-1])
-        self._flat = {key: self._alloc(key, (total,)).zero_() for key in _STATE_KEYS}
-        self.scalars = self._alloc("scalars", (2,)).zero_()
-        st = np.zeros(n, _TENSOR)
-        st["p"] = [p.data_ptr() for p in self.params]
-        for key, field in zip(_STATE_KEYS, ("m", "v", "slow")):
-            st[field] = self._flat[key].data_ptr() + 4 * self._offsets[:-1]
-        st["n"] = sizes
+        self._make_state(self._discover(model, alloc), _TENSOR, ("m", "v", "slow"))
         rows = [_gc_rows(p.shape, self.use_gc, self.gc_conv_only) for p in self.params]
-        st["rows"], st["row_len"] = [r[0] for r in rows], [r[1] for r in rows]
-        self._static = st
-        self._scalar_cache = {}
+        self._static["rows"], self._static["row_len"] = [r[0] for r in rows], [r[1] for r in rows]
 
     # ------------------------------------------------------------------ state
     def state_dict(self):
@@ -205,56 +298,17 @@ class Ranger(_FlatOptimizer):
                  "eps": self.eps, "weight_decay": self.weight_decay, "params": list(range(len(self.params))), "param_names": list(self.param_names)}
         return {"state": state, "param_groups": [group]}
 
-    def load_state_dict(self, sd):
-        groups = sd["param_groups"]
-        if len(groups) != 1 or list(groups[0]["params"]) != list(range(len(self.params))):
-            raise ValueError(f"Ranger.load_state_dict: one parameter group over {len(self.params)} parameters is expected")
-        g = groups[0]
-        if "param_names" in g and list(g["param_names"]) != self.param_names:
-            bad = [(a, b) for a, b in zip(g["param_names"], self.param_names) if a != b][:3]
-            raise ValueError(f"Ranger.load_state_dict: the parameter names differ, first {bad}")
-        for i, s in sd["state"].items():
-            if not 0 <= int(i) < len(self.params):
-                raise ValueError(f"Ranger.load_state_dict: state index {i} out of range")
-            for key in _STATE_KEYS:
-                if tuple(s[key].shape) != tuple(self.params[int(i)].shape):
-                    raise ValueError(f"Ranger.load_state_dict: state[{i}][{key}] {tuple(s[key].shape)}, expected {tuple(self.params[int(i)].shape)}")
+    def _take_group(self, g):
         self.lr, self.alpha, self.k = float(g["lr"]), float(g["alpha"]), int(g["k"])
         self.betas, self.eps, self.weight_decay = (float(g["betas"][0]), float(g["betas"][1])), float(g["eps"]), float(g["weight_decay"])
         self.N_sma_threshhold = g["N_sma_threshhold"]
-        for key in _STATE_KEYS:
-            self._flat[key].zero_()
-        self.steps = [0] * len(self.params)
-        for i, s in sd["state"].items():
-            self.steps[int(i)] = int(s["step"])
-            for key in _STATE_KEYS:
-                self._view(key, int(i)).copy_(s[key])
 
     # ------------------------------------------------------------------ the step
-    def _scalars_of(self, step, lr):
-        key = (step, lr)
-        hit = self._scalar_cache.get(key)
-        if hit is None:
-            rect, size = radam_step_size(step, self.betas[0], self.betas[1], self.N_sma_threshhold)
-            flags = (_lib.GPO_FLAG_RECTIFIED if rect else 0) | (_lib.GPO_FLAG_LOOKAHEAD if step % self.k == 0 else 0)
-            if len(self._scalar_cache) > 64:
-                self._scalar_cache.clear()
-            hit = self._scalar_cache[key] = (flags, size * lr)
-        return hit
+    def _step_scalars(self, step, lr):
+        rect, size = radam_step_size(step, self.betas[0], self.betas[1], self.N_sma_threshhold)
+        return (_lib.GPO_FLAG_RECTIFIED if rect else 0) | (_lib.GPO_FLAG_LOOKAHEAD if step % self.k == 0 else 0), size * lr
 
-    @torch.no_grad()
-    def step(self, param_grads, clip_norm=None, lr=None):
-        """One step over the parameters that have an entry in param_grads; a parameter without one is skipped and its step count does
-        not advance (p.grad is None in the reference).  clip_norm: clip_grad_norm_'s max_norm over these gradients, applied inside the
-        update (the gradients themselves are not scaled).  lr: this call's learning rate (default: the optimiser's)."""
-        lr = self.lr if lr is None else float(lr)
-        if clip_norm is not None and not float(clip_norm) > 0:
-            raise ValueError(f"Ranger.step: clip_norm {clip_norm} must be positive (or None)")
-        grads = self._collect(param_grads)
-        if not grads:
-            return
-        active = sorted(grads)
-        L = _lib.load()
+    def _before_step(self, active):
         first = [i for i in active if self.steps[i] == 0]
         if first:        # the reference creates a parameter's state at its first step: slow_buffer starts as a copy of the parameter
             dst, src = [self._view("slow_buffer", i) for i in first], [self.params[i].detach() for i in first]
@@ -263,25 +317,10 @@ class Ranger(_FlatOptimizer):
             else:
                 for d, s in zip(dst, src):
                     d.copy_(s)
-        tab = self._static[active]
-        tab["p"] = [self.params[i].data_ptr() for i in active]
-        tab["g"] = [grads[i][1].data_ptr() for i in active]
-        sc = []
-        for i in active:
-            self.steps[i] += 1
-            sc.append(self._scalars_of(self.steps[i], lr))
+
+    def _fill(self, tab, sc, max_norm):
         tab["flags"], tab["step_lr"] = [s[0] for s in sc], [s[1] for s in sc]
-        hyper = _lib.OptHyper(self.betas[0], self.betas[1], self.eps, self.alpha, self.weight_decay, float(clip_norm) if clip_norm is not None else 0.0)
-        ptr = _table_ptr(tab)
-        nbytes = L.gpo_ranger_step_workspace(ptr, len(active))
-        if nbytes <= 0:
-            _lib.check(-1, "gpo_ranger_step_workspace")
-        ws = self._workspace(nbytes)
-        with torch.cuda.device(self.device):
-            _lib.check(L.gpo_ranger_step(ptr, len(active), ctypes.byref(hyper), self.scalars.data_ptr(), ws.data_ptr(), ws.numel() * 4,
-                                         _stream(self.device)), "gpo_ranger_step")
-        if hasattr(self.model, "params_updated"):
-            self.model.params_updated()
+        return _lib.OptHyper(self.betas[0], self.betas[1], self.eps, self.alpha, self.weight_decay, max_norm)
 
 
 def adam_step_scalars(step, lr, beta1, beta2, weight_decay):
@@ -302,7 +341,8 @@ class Adam(_FlatOptimizer):
     maximize, capturable, differentiable and fused are torch's keywords for paths that are not built: they must be false or None;
     foreach is accepted and has no meaning here (one launch serves all tensors)."""
 
-    _who = "Adam"
+    _who, _entry, _query_takes_hyper = "Adam", "gpad_adam_step", True
+    _ptr = staticmethod(_adam_table_ptr)
     _decoupled = False
     _default_weight_decay = 0
 
@@ -327,18 +367,8 @@ class Adam(_FlatOptimizer):
                 raise NotImplementedError(f"{who}: {key}={value!r} is not built; only the plain step is (leave {key} at its default)")
         self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
         self.weight_decay, self.amsgrad = float(weight_decay), bool(amsgrad)
-        sizes = self._discover(model, alloc)
-        n, total = len(self.params), int(self._offsets[-1])
         self._state_keys = _ADAM_STATE_KEYS if self.amsgrad else _ADAM_STATE_KEYS[:2]
-        self._flat = {key: self._alloc(key, (total,)).zero_() for key in self._state_keys}
-        self.scalars = self._alloc("scalars", (2,)).zero_()
-        st = np.zeros(n, _ADAM_TENSOR)
-        st["p"] = [p.data_ptr() for p in self.params]
-        for key, field in zip(self._state_keys, ("m", "v", "vmax")):
-            st[field] = self._flat[key].data_ptr() + 4 * self._offsets[:-1]
-        st["n"] = sizes
-        self._static = st
-        self._scalar_cache = {}
+        self._make_state(self._discover(model, alloc), _ADAM_TENSOR, ("m", "v", "vmax"))
 
     # ------------------------------------------------------------------ state
     def _group(self):
@@ -355,15 +385,7 @@ class Adam(_FlatOptimizer):
                  for i, s in enumerate(self.steps) if s > 0}
         return {"state": state, "param_groups": [{**self._group(), "params": list(range(len(self.params))), "param_names": list(self.param_names)}]}
 
-    def load_state_dict(self, sd):
-        who = f"{self._who}.load_state_dict"
-        groups = sd["param_groups"]
-        if len(groups) != 1 or list(groups[0]["params"]) != list(range(len(self.params))):
-            raise ValueError(f"{who}: one parameter group over {len(self.params)} parameters is expected")
-        g = groups[0]
-        if "param_names" in g and list(g["param_names"]) != self.param_names:
-            bad = [(a, b) for a, b in zip(g["param_names"], self.param_names) if a != b][:3]
-            raise ValueError(f"{who}: the parameter names differ, first {bad}")
+    def _check_group(self, g, who):
         for key in ("maximize", "capturable", "differentiable", "fused"):
             if g.get(key):
                 raise NotImplementedError(f"{who}: the saved group has {key}={g[key]!r}, which is not built")
@@ -372,65 +394,19 @@ class Adam(_FlatOptimizer):
         if "decoupled_weight_decay" in g and bool(g["decoupled_weight_decay"]) != self._decoupled:
             raise ValueError(f"{who}: the saved group has decoupled_weight_decay={g['decoupled_weight_decay']} "
                              f"({'AdamW' if g['decoupled_weight_decay'] else 'Adam'}), this optimiser is {self._who}")
-        for i, s in sd["state"].items():
-            if not 0 <= int(i) < len(self.params):
-                raise ValueError(f"{who}: state index {i} out of range")
-            for key in self._state_keys:
-                if key not in s or tuple(s[key].shape) != tuple(self.params[int(i)].shape):
-                    raise ValueError(f"{who}: state[{i}][{key}] {tuple(s[key].shape) if key in s else 'is missing'}, expected {tuple(self.params[int(i)].shape)}")
+
+    def _take_group(self, g):
         self.lr, self.betas = float(g["lr"]), (float(g["betas"][0]), float(g["betas"][1]))
         self.eps, self.weight_decay = float(g["eps"]), float(g["weight_decay"])
-        self._scalar_cache = {}
-        for key in self._state_keys:
-            self._flat[key].zero_()
-        self.steps = [0] * len(self.params)
-        for i, s in sd["state"].items():
-            self.steps[int(i)] = int(float(s["step"]))          # a 0-d tensor (torch >= 1.12) or a number
-            for key in self._state_keys:
-                self._view(key, int(i)).copy_(s[key])
 
     # ------------------------------------------------------------------ the step
-    def _scalars_of(self, step, lr):
-        key = (step, lr)
-        hit = self._scalar_cache.get(key)
-        if hit is None:
-            if len(self._scalar_cache) > 64:
-                self._scalar_cache.clear()
-            hit = self._scalar_cache[key] = adam_step_scalars(step, lr, self.betas[0], self.betas[1], self.weight_decay)
-        return hit
+    def _step_scalars(self, step, lr):
+        return adam_step_scalars(step, lr, self.betas[0], self.betas[1], self.weight_decay)
 
-    @torch.no_grad()
-    def step(self, param_grads, clip_norm=None, lr=None):
-        """One step over the parameters that have an entry in param_grads; a parameter without one is skipped and its step count does
-        not advance (p.grad is None in torch).  clip_norm: clip_grad_norm_'s max_norm over these gradients, applied inside the update
-        (the gradients themselves are not scaled).  lr: this call's learning rate (default: the optimiser's)."""
-        lr = self.lr if lr is None else float(lr)
-        if clip_norm is not None and not float(clip_norm) > 0:
-            raise ValueError(f"{self._who}.step: clip_norm {clip_norm} must be positive (or None)")
-        grads = self._collect(param_grads)
-        if not grads:
-            return
-        active = sorted(grads)
-        L = _lib.load()
-        tab = self._static[active]
-        tab["p"] = [self.params[i].data_ptr() for i in active]
-        tab["g"] = [grads[i][1].data_ptr() for i in active]
-        sc = [self._scalars_of(self.steps[i] + 1, lr) for i in active]
+    def _fill(self, tab, sc, max_norm):
         tab["step_size"], tab["bc2_sqrt"], tab["decay"] = [s[0] for s in sc], [s[1] for s in sc], [s[2] for s in sc]
-        hyper = _lib.AdamHyper(self.betas[0], self.betas[1], self.eps, self.weight_decay, float(clip_norm) if clip_norm is not None else 0.0,
-                               _lib.GPAD_MODE_ADAMW if self._decoupled else _lib.GPAD_MODE_ADAM, int(self.amsgrad))
-        ptr = _adam_table_ptr(tab)
-        nbytes = L.gpad_adam_step_workspace(ptr, len(active), ctypes.byref(hyper))
-        if nbytes <= 0:
-            _lib.check(-1, "gpad_adam_step_workspace")
-        ws = self._workspace(nbytes)
-        with torch.cuda.device(self.device):
-            _lib.check(L.gpad_adam_step(ptr, len(active), ctypes.byref(hyper), self.scalars.data_ptr(), ws.data_ptr(), ws.numel() * 4,
-                                        _stream(self.device)), "gpad_adam_step")
-        for i in active:
-            self.steps[i] += 1
-        if hasattr(self.model, "params_updated"):
-            self.model.params_updated()
+        return _lib.AdamHyper(self.betas[0], self.betas[1], self.eps, self.weight_decay, max_norm,
+                              _lib.GPAD_MODE_ADAMW if self._decoupled else _lib.GPAD_MODE_ADAM, int(self.amsgrad))
 
 
 class AdamW(Adam):
@@ -470,17 +446,9 @@ def clip_grad_norm_(param_grads, max_norm, alloc=None):
         raise ValueError("clip_grad_norm_: no gradients")
     tab = np.zeros(len(seen), _TENSOR)
     tab["g"], tab["n"] = list(seen), [g.numel() for g in seen.values()]
-    L = _lib.load()
-    ptr = _table_ptr(tab)
-    nbytes = L.gpo_clip_grad_norm_workspace(ptr, len(tab))
-    if nbytes <= 0:
-        _lib.check(-1, "gpo_clip_grad_norm_workspace")
     alloc = alloc or _default_alloc(dev)
-    ws = alloc("workspace", (max(int(nbytes) // 4, 64),))
-    scalars = alloc("scalars", (2,))
-    with torch.cuda.device(dev):
-        _lib.check(L.gpo_clip_grad_norm(ptr, len(tab), float(max_norm), scalars.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream(dev)),
-                   "gpo_clip_grad_norm")
+    scalars = _launch("gpo_clip_grad_norm", dev, lambda nbytes: alloc("workspace", (max(int(nbytes) // 4, 64),)), lambda: alloc("scalars", (2,)),
+                      _table_ptr(tab), len(tab), (), (float(max_norm),))
     return scalars[0]
 
 
@@ -530,12 +498,6 @@ class GradAccumulator:
         """optimizer.zero_grad(): no parameter has an accumulated gradient.  Nothing is written: the next add() overwrites."""
         self._live = set()
 
-    def _workspace(self, nbytes):
-        if self._ws is None or self._ws.numel() * 4 < nbytes:
-            self._ws = self._alloc("workspace", (max(int(nbytes) // 4, 64),))
-            assert self._ws.data_ptr() % 256 == 0, "workspace buffers must be 256-byte aligned"
-        return self._ws
-
     def _table(self, param_grads):
         """-> (parameter indices, gpo_tensor table) of one add(): the parameters of param_grads and the live ones, in index order."""
         grads = self.optimizer._collect(param_grads)
@@ -546,15 +508,8 @@ class GradAccumulator:
         return entries, tab, grads
 
     def _launch(self, tab, scale, max_norm):
-        L = _lib.load()
-        ptr = _table_ptr(tab)
-        nbytes = L.gpc_grad_accumulate_workspace(ptr, len(tab))
-        if nbytes <= 0:
-            _lib.check(-1, "gpc_grad_accumulate_workspace")
-        ws = self._workspace(nbytes)
-        with torch.cuda.device(self.device):
-            _lib.check(L.gpc_grad_accumulate(ptr, len(tab), scale, max_norm, self.scalars.data_ptr(), ws.data_ptr(), ws.numel() * 4,
-                                             _stream(self.device)), "gpc_grad_accumulate")
+        _launch("gpc_grad_accumulate", self.device, lambda nbytes: _workspace(self, nbytes), self.scalars, _table_ptr(tab), len(tab), (),
+                (scale, max_norm))
 
     def _world(self, group):
         import torch.distributed as dist

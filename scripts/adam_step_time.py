@@ -82,11 +82,12 @@ def kernel_count(say):
             names = [r.get("Kernel_Name", "") for r in rows]
             copies = sum("__amd_rocclr_" in n for n in names)       # the runtime's own copy kernels, where the trace lists them
             counts[steps] = (len(names) - copies, copies)
-            mine = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]) for r in rows if "adam_" in r.get("Kernel_Name", ""))[-9:]
+            mine = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]) for r in rows
+                          if "adam_" in r.get("Kernel_Name", "") or "finalize_kernel" in r.get("Kernel_Name", ""))[-9:]
             if steps == 4 and len(mine) == 9:
                 per = {}
                 for a, b, n in mine:
-                    key = next(k for k in ("adam_reduce_kernel", "adam_finalize_kernel", "adam_update_kernel") if k in n)
+                    key = next(k for k in ("adam_reduce_kernel", "finalize_kernel", "adam_update_kernel") if k in n)
                     per[key] = per.get(key, 0.0) + (b - a) / 3e3
                 say("kernel time per step (mean of the last three steps under the tracer): "
                     + ", ".join(f"{k} {v:.1f} us" for k, v in per.items()) + f"; sum {sum(per.values()):.1f} us")

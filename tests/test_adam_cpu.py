@@ -48,10 +48,17 @@ def test_header_prototypes_and_exports_agree():
     assert set(re.findall(r" T (gpad_[a-z0-9_]+)", out)) == declared
     assert "adam.hip" in build.SOURCES
     src = open(os.path.join(ROOT, "givepose_amd", "csrc", "adam.hip")).read()
-    assert not re.search(r"\batomic\w*\s*\(", src)                    # no atomic in the family
+    shared = open(os.path.join(ROOT, "givepose_amd", "csrc", "flat_tensors.hpp")).read()          # the family's other half
+    assert '#include "flat_tensors.hpp"' in src
+    assert not re.search(r"\batomic\w*\s*\(", src + shared)                    # no atomic in the family
     body = src.split("int gpad_adam_step(")[1]
     assert len(re.findall(r"hipLaunchKernelGGL", body)) == _lib.GPAD_STEP_LAUNCHES == 3
-    assert "hipMalloc" not in src and "Synchronize" not in src and body.count("hipMemcpyAsync") == 1 and "DeviceToHost" not in src
+    for text in (src, shared):
+        assert "hipMalloc" not in text and "Synchronize" not in text and "DeviceToHost" not in text
+    # one copy per step: none in adam.hip, one in the header, inside send_tables, which the step calls once
+    assert src.count("hipMemcpyAsync") == 0 and shared.count("hipMemcpyAsync") == 1
+    assert shared.split("int send_tables(")[1].split("\n}\n")[0].count("hipMemcpyAsync(") == 1
+    assert len(re.findall(r"\bsend_tables\s*\(", body)) == 1 and len(re.findall(r"\bsend_tables\s*\(", src)) == 1
     consts = {k: int(v) for k, v in re.findall(r"#define (GPAD_[A-Z_]+) (\d+)", hdr)}
     assert consts == {"GPAD_STEP_LAUNCHES": _lib.GPAD_STEP_LAUNCHES, "GPAD_MAX_TENSORS": _lib.GPAD_MAX_TENSORS, "GPAD_MODE_ADAM": _lib.GPAD_MODE_ADAM,
                       "GPAD_MODE_ADAMW": _lib.GPAD_MODE_ADAMW}

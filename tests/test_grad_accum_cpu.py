@@ -113,7 +113,8 @@ def test_header_prototypes_and_exports_agree():
     assert set(re.findall(r" T (gpc_[a-z0-9_]+)", out)) == declared
     assert "accum.hip" in build.SOURCES
     src = open(os.path.join(ROOT, "givepose_amd", "csrc", "accum.hip")).read()
-    assert not re.search(r"\batomic\w*\s*\(", src, flags=re.I)                    # no atomic in the family
+    shared = open(os.path.join(ROOT, "givepose_amd", "csrc", "flat_tensors.hpp")).read()
+    assert '#include "flat_tensors.hpp"' in src and not re.search(r"\batomic\w*\s*\(", src + shared, flags=re.I)                    # no atomic in the family
     entry = src.split("int gpc_grad_accumulate(")[1].split('}  // extern "C"')[0]
     assert len(re.findall(r"hipLaunchKernelGGL", entry)) == _lib.GPC_ACCUM_LAUNCHES == 3
     consts = {k: int(v) for k, v in re.findall(r"#define (GPC_[A-Z_]+) (\d+)", hdr)}

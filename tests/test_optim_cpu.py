@@ -107,7 +107,8 @@ def test_header_prototypes_and_exports_agree():
     assert set(re.findall(r" T (gpo_[a-z0-9_]+)", out)) == declared
     assert "optim.hip" in build.SOURCES
     src = open(os.path.join(ROOT, "givepose_amd", "csrc", "optim.hip")).read()
-    assert not re.search(r"\batomic\w*\s*\(", src)                    # no atomic in the family
+    shared = open(os.path.join(ROOT, "givepose_amd", "csrc", "flat_tensors.hpp")).read()
+    assert '#include "flat_tensors.hpp"' in src and not re.search(r"\batomic\w*\s*\(", src + shared)                    # no atomic in the family
     assert len(re.findall(r"hipLaunchKernelGGL", src.split("int gpo_ranger_step(")[1].split("long long gpo_clip")[0])) == _lib.GPO_STEP_LAUNCHES
     consts = {k: int(v) for k, v in re.findall(r"#define (GPO_[A-Z_]+) (\d+)", hdr)}
     assert consts == {"GPO_CHUNK": _lib.GPO_CHUNK, "GPO_STEP_LAUNCHES": _lib.GPO_STEP_LAUNCHES, "GPO_CLIP_LAUNCHES": _lib.GPO_CLIP_LAUNCHES,
@@ -131,6 +132,32 @@ def test_header_prototypes_and_exports_agree():
         bad[field][1] = value
         assert lib.gpo_ranger_step_workspace(optim._table_ptr(bad), 3) == 0, (field, value)
     assert b"tensor 1" in lib.gp_last_error()
+
+
+def test_the_flat_tensor_families_share_one_text():
+    """What the gpo_*, gpc_* and gpad_* families have in common -- the reductions, the quad moves, the finalize kernel, the chunk record
+    -- is defined in csrc/flat_tensors.hpp and in none of the three files: the norm's bits are equal across them by construction."""
+    from givepose_amd import build
+    csrc = os.path.join(ROOT, "givepose_amd", "csrc")
+    shared = open(os.path.join(csrc, "flat_tensors.hpp")).read()
+    family = {f: open(os.path.join(csrc, f)).read() for f in ("optim.hip", "accum.hip", "adam.hip")}
+    definitions = [r"\bfloat\s+wave_sum\s*\(", r"\bfloat\s+wg_sum\s*\(", r"\bf32x4\s+load_quad\s*\(", r"\bvoid\s+store_quad\s*\(", r"\bbool\s+al16\s*\(",
+                   r"\blong long\s+up256\s*\(", r"\bstruct\s+Chunk\b", r"\bvoid\s+\w*finalize_kernel\s*\(", r"\bfloat\s+sq_add\s*\(",
+                   r"\bint\s+send_tables\s*\(", r"\bstruct\s+Plan\b"]
+    for d in definitions:
+        assert len(re.findall(d, shared)) == 1, d
+        for f, text in family.items():
+            assert not re.search(d, text), (d, f)
+    for f, text in family.items():
+        assert text.count('#include "flat_tensors.hpp"') == 1, f
+        assert "finalize_kernel" in text and not re.search(r"\b\w+_finalize_kernel\b", text), f          # each launches the one definition
+        assert not re.search(r"__fmul_rn\((\w+(?:\[\w+\])?), \1\)", text) and "__builtin_fmaf" not in text and "sq_add(" in text, f      # one way to square
+        assert not re.search(r"#define\s+GP\w+_CHECK\b", text), f
+    assert "__builtin_fmaf(x, x, sq)" in shared and len(re.findall(r"#define\s+FLAT_CHECK\b", shared)) == 1
+    # included by exactly the three, and a dependency of the build
+    users = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".hpp")) and '"flat_tensors.hpp"' in open(os.path.join(csrc, f)).read())
+    assert users == ["accum.hip", "adam.hip", "optim.hip"]
+    assert "flat_tensors.hpp" in open(build.__file__).read()
 
 
 class _Tiny(torch.nn.Module):
